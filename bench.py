@@ -3,17 +3,24 @@
 workload (configs[2]: wdas_cloud.json at 1920x1080, 256 spp, one MI355X), on the synthetic 512^3
 cloud stand-in (the reference's wdas_cloud.nvdb is not available).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR] [--full]
 
 One step = one full frame (every wave of the configuration) rendered into a zeroed film on every
 rank, plus — for N > 1 — the RCCL sum of the films over xGMI.
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figures and the
+integrator kernel's roofline, which comes from the timed steps' own events and counters).  `--dump-outputs DIR`
+writes the film of the last timed step (what a caller of the timed path receives: float32 [H][W][4], XYZ sums and
+the sample count) to DIR/film.npy; the inputs are procedural and seeded, so the same arguments give the same
+film from run to run.  Everything else -- the drop-in frames and first call, the CPU baseline with its film
+parity, and for N > 1 the strong-scaling frames -- takes runs of its own and is measured only with `--full`.
 
 Multi-GPU.  `--gpus N` runs N ranks, one per GPU: under torchrun (WORLD_SIZE must equal N), or, when
 WORLD_SIZE is unset, by starting torch.distributed.run itself before anything touches the GPU.
   * default `--mode weak` (the driver's SCALE runs): every rank renders its own block of the C3
     frame's 256 waves (rank r: waves r*256+1 .. (r+1)*256), so N = 1 is exactly BENCH's C3 line and
     the per-GPU work is fixed;
-  * for N > 1 the line also carries `scaling_strong`: the C3 frame (256 waves) and the C5 frame
+  * for N > 1 the `--full` line also carries `scaling_strong`: the C3 frame (256 waves) and the C5 frame
     (BASELINE.json configs[4], 3840x2160 at 1024 spp) each dealt across the N ranks and timed the same
     way (barrier + synchronize, max over ranks, film all-reduce inside the step): the strong scaling
     that north_star's ">= 6x at 8 GPUs" asks about (`--strong-configs`, '' to skip); and the C3 frame in
@@ -27,7 +34,7 @@ The JSON line also carries:
                 the 8 TB/s HBM peak; `traffic` = PMC-measured HBM bytes per launch from the newest
                 committed profiles/<round>_<config>_pmc.json (a builder rocprofv3 --pmc pass, named in
                 `traffic_source`), else null.
-  cpu_baseline  the CPU oracle (headless restatement of the reference worker pool, main.cpp:62-87)
+  cpu_baseline  (`--full`) the CPU oracle (headless restatement of the reference worker pool, main.cpp:62-87)
                 timed on this host's cores on a bounded sample (whole waves of the same frame).
 """
 from __future__ import annotations
@@ -462,6 +469,28 @@ def timed_frames(it, rank, world, spp, mode, steps, warmup, stream, launch_ms=No
     return time.perf_counter() - t_start
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, film) -> None:
+    """--dump-outputs: the film of the last timed step (for N > 1 the all-reduced one) as DIR/film.npy, float32
+    [H][W][4] (XYZ sums, sample count).  A film over DUMP_MAX_BYTES (C5's 4K frame) is written as a fixed, seeded
+    sample of its pixels, [n][4], with the pixels' flat indices (row * width + column) in DIR/film_pixels.npy."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.nbytes > DUMP_MAX_BYTES:
+        pixels = film.shape[0] * film.shape[1]
+        n = DUMP_MAX_BYTES // (film.shape[2] * 4 + 8)  # per pixel: its float32 channels + its float64 index
+        idx = np.sort(np.random.default_rng(20240607).choice(pixels, size=n, replace=False))
+        np.save(d / "film_pixels.npy", idx.astype(np.float64))
+        film = film.reshape(pixels, film.shape[2])[idx]
+    np.save(d / "film.npy", film)
+    log(f"bench: wrote {d / 'film.npy'} {film.shape} float32")
+
+
 ALONE_BIG_SAMPLES = 1e9  # frames this large (C5: 8.5e9 samples, ~5 s on one GPU) are timed alone at 1 + 1 frames
 
 
@@ -542,8 +571,14 @@ def main():
     ap.add_argument("--film-order", choices=["ordered", "atomic"], default="ordered",
                     help="ordered (default): each pixel's samples added in wave order, the reference's film bit for bit "
                          "(vpt_gpu_set_film_order); atomic: fp32 atomics in completion order (A/B runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the reference-API (drop-in) frame timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the drop-in frames and first call, the CPU baseline "
+                         "and film parity, and for N > 1 the strong-scaling frames (off: the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's film (float32 [H][W][4]) to DIR/film.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and film parity")
+    ap.add_argument("--no-dropin", action="store_true",
+                    help="--full: skip the reference-API (drop-in) frame timing")
     ap.add_argument("--dropin-frames", type=int, default=3)
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline work (3 runs)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -566,8 +601,8 @@ def main():
     # (not under rocprofv3: its preloaded library has initialised the GPU in this process, which then must not
     # start another program)
     profiled = any(k.startswith("ROCPROF") for k in os.environ)
-    if (world == 1 and not args.no_dropin and not profiled and args.rng_mode == "reference" and args.spp is None
-            and args.grid_n is None):
+    if (args.full and world == 1 and not args.no_dropin and not profiled and args.rng_mode == "reference"
+            and args.spp is None and args.grid_n is None):
         # the drop-in runs in a child process, before this one touches the GPU
         from volume_path_tracer_amd.scenes import workload as _workload
 
@@ -622,9 +657,11 @@ def main():
     film = it.film_host()
     assert (film[..., 3] == D.total_samples_per_pixel(world, spp, args.mode)).all(), "sample-count channel mismatch"
     del it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, film)
 
     strong = None
-    if world > 1 and args.strong_configs and args.rng_mode == "reference":
+    if args.full and world > 1 and args.strong_configs and args.rng_mode == "reference":
         strong = strong_scaling([c for c in args.strong_configs.split(",") if c], dens, rank, world, dev, sdev,
                                 args.steps, args.warmup, stream)
 
@@ -691,7 +728,7 @@ def main():
                 dropin["bit_identical_to_one_launch"] = differ == 0
                 dropin["pixels_differing_from_one_launch"] = differ
             out["dropin"] = dropin
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, ref_film, k = cpu_baseline(wl, dens, temp, args.cpu_budget)
             out["cpu_baseline"] = cb
             out["parity"] = film_parity(wl, dens, temp, ref_film, k, dev.index)

@@ -56,6 +56,27 @@ def test_strong_scaling_configs_share_the_cloud():
         bench.strong_scaling(["c3:fast"], None, 0, 2, torch.device("cuda", 0), torch.device("cpu"), 1, 0, None)
 
 
+def test_dump_outputs_whole_film_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a film within the size cap is written whole as float32; a larger one as the same seeded
+    sample of its pixels on every call, with the pixels' flat indices beside it."""
+    import numpy as np
+
+    film = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    bench.dump_outputs(tmp_path / "a", film)
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, film)
+    assert not (tmp_path / "a" / "film_pixels.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 24)  # room for 10 of the 30 pixels
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, film)
+    got, idx = np.load(tmp_path / "b" / "film.npy"), np.load(tmp_path / "b" / "film_pixels.npy")
+    assert got.shape == (10, 4) and got.dtype == np.float32 and idx.dtype == np.float64
+    assert got.nbytes + idx.nbytes <= 10 * 24 and len(set(idx)) == 10
+    assert np.array_equal(got, film.reshape(30, 4)[idx.astype(int)])
+    assert np.array_equal(got, np.load(tmp_path / "c" / "film.npy"))
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "film_pixels.npy"))
+
+
 def test_request_roofline_uses_the_configs_own_counter_pass():
     """Counter passes of other workloads (tools/kernel_counters.sh ... --grid-n N: bench_args set) never
     feed the bench line's request_frac."""

@@ -137,7 +137,8 @@ def test_bench_gpus2_spawns_two_ranks(tmp_path):
     assert_hip_untouched()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--spp", "2", "--no-cpu-baseline", "--backend", "gloo", "--one-device", "--strong-configs", "c3,c3:pixel"],
+                        "--spp", "2", "--full", "--no-cpu-baseline", "--backend", "gloo", "--one-device",
+                        "--strong-configs", "c3,c3:pixel"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -22,4 +22,4 @@ PASSES
 python3 tools/pmc_traffic.py ${TAG}_${CFG} $CFG $(python3 -c "from volume_path_tracer_amd.scenes import workload; print(workload('$CFG').spp)") $O/pmc_* || exit 1
 cp profiles/${TAG}_${CFG}_pmc.json $O/
 step rocprof 600 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --config $CFG --no-cpu-baseline --no-dropin
-if [ "$CFG" = "c3" ]; then step bench 900 python3 bench.py; tail -1 $O/bench.log | cut -c1-400; fi
+if [ "$CFG" = "c3" ]; then step bench 900 python3 bench.py --full; tail -1 $O/bench.log | cut -c1-400; fi
