@@ -438,11 +438,11 @@ int vpt_gpu_film_flush_to_host(vpt_gpu_ctx* ctx, float* film_device, float* film
  * (hipDeviceSynchronize, and hipFree / hipHostMalloc / hipHostFree may) waits for an open feed's lanes to
  * give up: wait for streams instead.  The context's own calls that wait for its launches (vpt_gpu_sync,
  * vpt_gpu_film_clear, vpt_gpu_film_add_to_host, vpt_gpu_counters, vpt_gpu_profile, vpt_gpu_set_tuning,
- * vpt_gpu_set_latency_tuning, vpt_gpu_set_rng_mode, vpt_gpu_set_tile_costs, vpt_gpu_set_job_permutation,
- * and vpt_gpu_tile_costs before its first cost pass) return VPT_E_STATE while a feed of the context is
- * launched and not closed, instead of waiting 30 s for its lanes to give up.  A destroyed feed's memory is
- * kept by the context for the next vpt_gpu_feed_open (freed by vpt_gpu_destroy).  Feeds use a host-pinned
- * ring (8 bytes per window slot) and run the reference RNG mode. */
+ * vpt_gpu_set_full_tuning, vpt_gpu_set_latency_tuning, vpt_gpu_set_rng_mode, vpt_gpu_set_tile_costs,
+ * vpt_gpu_set_job_permutation, and vpt_gpu_tile_costs before its first cost pass) return VPT_E_STATE while a
+ * feed of the context is launched and not closed, instead of waiting 30 s for its lanes to give up.  A
+ * destroyed feed's memory is kept by the context for the next vpt_gpu_feed_open (freed by vpt_gpu_destroy).
+ * Feeds use a host-pinned ring (8 bytes per window slot) and run the reference RNG mode. */
 typedef struct vpt_gpu_feed vpt_gpu_feed;
 int vpt_gpu_feed_open(vpt_gpu_ctx* ctx, float* film_device, void* hip_stream, uint64_t window, vpt_gpu_feed** out);
 int vpt_gpu_feed_push(vpt_gpu_feed* feed, const uint64_t* jids, uint64_t n);
@@ -498,9 +498,22 @@ int vpt_gpu_counters(vpt_gpu_ctx* ctx, vpt_counters* out, int reset);
  * for gate_eval lanes likewise; grid_blocks overrides the persistent grid size; the ray walk
  * repeats in an inner loop while >= gate_walk lanes walk (0: one step per pass).
  * Pass <= 0 (gate_idle, gate_walk < 0) to keep a value; gate_idle 0 is rejected (VPT_E_INVALID): a
- * wavefront with no walking lane must run its waiting blocks. */
+ * wavefront with no walking lane must run its waiting blocks.
+ * A context keeps three gate sets: the context's (partly filled launches, feeds, debug launches), the
+ * full-launch set (production launches of the throughput kernel: full frames such as C3 / C4) and the latency
+ * set (vpt_gpu_set_latency_tuning).  vpt_gpu_set_tuning writes the first two. */
 int vpt_gpu_set_tuning(vpt_gpu_ctx* ctx, int gate_min, int gate_idle, int grid_blocks, int gate_eval,
                        int gate_walk);
+/* The full-launch gate set alone (meaning and "keep" conventions as in vpt_gpu_set_tuning; gate_idle 0 is
+ * rejected): launches that run the throughput kernel outside feeds and debug launches read it.  Defaults: the
+ * context's gates, with gate_idle 4 for the density kernel (its partly filled launches keep 8).  Results never
+ * depend on it. */
+int vpt_gpu_set_full_tuning(vpt_gpu_ctx* ctx, int gate_min, int gate_idle, int gate_eval, int gate_walk);
+/* A gate set's values (gates[4]: gate_min, gate_idle, gate_eval, gate_walk; NULL to skip) and the set the
+ * context's last launch read (*last_launch_set; -1 before the first launch; NULL to skip).  Host state only:
+ * no wait. */
+enum { VPT_GATES_CONTEXT = 0, VPT_GATES_LATENCY = 1, VPT_GATES_FULL = 2 };
+int vpt_gpu_gate_info(const vpt_gpu_ctx* ctx, int set, int* gates, int* last_launch_set);
 /* Latency-bound launches: a launch with fewer work items than its grid has lanes (e.g. C1, 4 096
  * jobs) lasts as long as its slowest job.  Such launches spread their items over the grid's
  * wavefronts -- the first wave_lanes lanes of each wavefront take jobs (0 = auto: 1 while items /

@@ -99,6 +99,7 @@ VPT_RNG_REFERENCE, VPT_RNG_PIXEL = 0, 1
 VPT_ORDER_JID, VPT_ORDER_COST_WAVE_MAJOR, VPT_ORDER_COST_TILE_MAJOR, VPT_ORDER_COST_TAIL = 0, 1, 2, 3
 VPT_ORDER_COST_SAME_TILE = 4
 VPT_FILM_ATOMIC, VPT_FILM_ORDERED = 0, 1
+VPT_GATES_CONTEXT, VPT_GATES_LATENCY, VPT_GATES_FULL = 0, 1, 2
 EVENT_NAMES = ("new_ray", "sampled_point", "null", "scatter_terminated", "scatter", "absorbed")
 
 
@@ -247,6 +248,10 @@ def lib() -> C.CDLL:
     L.vpt_gpu_set_tuning.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "vpt_gpu_set_latency_tuning"):  # (older builds in A/B runs lack it)
         L.vpt_gpu_set_latency_tuning.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "vpt_gpu_set_full_tuning"):  # (older builds in A/B runs lack them)
+        L.vpt_gpu_set_full_tuning.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "vpt_gpu_gate_info"):
+        L.vpt_gpu_gate_info.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.vpt_gpu_launch_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.vpt_last_error.restype = C.c_char_p
     L.vpt_synth_grid.argtypes = [C.c_int, C.c_int]

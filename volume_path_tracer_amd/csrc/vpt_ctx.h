@@ -27,6 +27,11 @@
 #define VPT_DEFAULT_JOB_ORDER VPT_ORDER_COST_SAME_TILE
 #endif
 
+// The density kernel's full-launch gate_idle (vpt_gpu_set_full_tuning); A/B builds override it.
+#ifndef VPT_DEFAULT_FULL_GATE_IDLE
+#define VPT_DEFAULT_FULL_GATE_IDLE 4
+#endif
+
 // The density-only kernel takes its run-skipping variant when this share of the interior cells has a run
 // radius >= 2 (C2's cube: 1.0; the cloud: below it; r06zb: C3 on it 21 % slower).
 #ifndef VPT_RUNS_MIN_FRACTION
@@ -88,6 +93,11 @@ struct vpt_gpu_ctx {
   vpt::DevScene* scene_lat_dev = nullptr;
   int lat_gate[4] = {1, 65, 1, 1};   // gate_min, gate_idle, gate_eval, gate_walk
   int lat_wave_lanes = 0;            // 0: spread the items evenly over the grid's wavefronts
+  // Full launches (the throughput kernel outside feeds and debug launches): a third device copy of the scene
+  // with full_gate[] in place of the gates, so that tuning them leaves partly filled launches alone.
+  vpt::DevScene* scene_full_dev = nullptr;
+  int full_gate[4] = {0, 0, 0, 0};   // gate_min, gate_idle, gate_eval, gate_walk (set at creation)
+  int last_gate_set = -1;            // the gate set the last launch read (VPT_GATES_*; vpt_gpu_gate_info)
   hipStream_t stream = nullptr;
   bool use_runs = false;             // density-only kernel variant with run skipping (see create)
   int pixel_chunk = 0;               // throughput mode: pixels per work item (0 = auto, see render)

@@ -119,6 +119,12 @@ int push_scene(vpt_gpu_ctx* ctx) {
   lat.wave_lanes = ctx->lat_wave_lanes;
   VPT_HIP(hipMemcpyAsync(ctx->scene_dev, &ctx->scene, sizeof(vpt::DevScene), hipMemcpyHostToDevice, ctx->stream));
   VPT_HIP(hipMemcpyAsync(ctx->scene_lat_dev, &lat, sizeof(vpt::DevScene), hipMemcpyHostToDevice, ctx->stream));
+  vpt::DevScene full = ctx->scene;
+  full.gate_min = ctx->full_gate[0];
+  full.gate_idle = ctx->full_gate[1];
+  full.gate_eval = ctx->full_gate[2];
+  full.gate_walk = ctx->full_gate[3];
+  VPT_HIP(hipMemcpyAsync(ctx->scene_full_dev, &full, sizeof(vpt::DevScene), hipMemcpyHostToDevice, ctx->stream));
   VPT_HIP(hipStreamSynchronize(ctx->stream));
   return VPT_OK;
 }
@@ -179,6 +185,7 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->prof);
   (void)hipFree(ctx->scene_dev);
   (void)hipFree(ctx->scene_lat_dev);
+  (void)hipFree(ctx->scene_full_dev);
   (void)hipFree(ctx->order);
   (void)hipFree(ctx->perm);
   (void)hipFree(ctx->samples);
@@ -478,8 +485,13 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
                        : ctx->use_runs
                            ? (dbg ? vpt::vpt_integrate_kernel<false, true, true> : vpt::vpt_integrate_kernel<false, false, true>)
                            : (dbg ? vpt::vpt_integrate_kernel<false, true, false> : vpt::vpt_integrate_kernel<false, false, false>);
+    // (production launches of the throughput kernel read the full-launch gates, vpt_gpu_set_full_tuning; a
+    // latency-bound one on it keeps the latency copy: its wave_lanes)
+    if (!dbg && scene == ctx->scene_dev) scene = ctx->scene_full_dev;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
   }
+  ctx->last_gate_set = scene == ctx->scene_full_dev ? VPT_GATES_FULL
+                       : scene == ctx->scene_lat_dev ? VPT_GATES_LATENCY : VPT_GATES_CONTEXT;  // (vpt_gpu_gate_info)
   VPT_HIP(hipGetLastError());
   const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
   if (samples) {  // the film, pixel by pixel in wave order (sample counts included)
@@ -676,8 +688,8 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   ctx->scene.gate_min = has_temperature ? 8 : 6;
   // The temperature kernel runs its rare blocks at any count only once no lane walks (same-tile order; C4 at
   // gate_idle 8 / 4 / 2 / 1: 67.2-67.4 / 64.2-64.3 / 62.8 / 61.5 ms, profiles/r06zj_c4_gates.txt,
-  // r06zk_gates_idle.txt).  (C3 measured 317.7 ms at 4 vs 321.9 at 8, but the density kernel's partly filled
-  // launches -- C2, a GPU's share -- read the same gates and were tuned at 8: not changed.)
+  // r06zk_gates_idle.txt).  The density kernel's partly filled launches -- C2, a GPU's share -- were tuned at 8
+  // and keep it; its full launches read a gate set of their own (full_gate, below).
   ctx->scene.gate_idle = has_temperature ? 1 : 8;
   ctx->scene.gate_eval = 36;
   // The temperature kernel's walk loops while any lane walks (gate_walk 1) since the same-tile order: C4 67.3-67.8
@@ -688,6 +700,13 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   ctx->scene.tile_area = (uint32_t)(ctx->scene.tw * ctx->scene.th);
   VPT_HIP(hipMalloc((void**)&ctx->scene_dev, sizeof(vpt::DevScene)));
   VPT_HIP(hipMalloc((void**)&ctx->scene_lat_dev, sizeof(vpt::DevScene)));
+  VPT_HIP(hipMalloc((void**)&ctx->scene_full_dev, sizeof(vpt::DevScene)));
+  // Full launches' gates (vpt_gpu_set_full_tuning): the context's, and for the density kernel gate_idle
+  // VPT_DEFAULT_FULL_GATE_IDLE (DESIGN.md section 4 has the sweep).
+  ctx->full_gate[0] = ctx->scene.gate_min;
+  ctx->full_gate[1] = has_temperature ? ctx->scene.gate_idle : VPT_DEFAULT_FULL_GATE_IDLE;
+  ctx->full_gate[2] = ctx->scene.gate_eval;
+  ctx->full_gate[3] = ctx->scene.gate_walk;
   if ((rc = push_scene(ctx.get()))) return rc;
   lap(2);
   *out = ctx.release();
@@ -1159,6 +1178,17 @@ int vpt_gpu_film_flush_to_host(vpt_gpu_ctx* ctx, float* film_device, float* film
 
 }  // extern "C"
 
+namespace {
+// The setters' conventions for one gate set (gate_min, gate_idle, gate_eval, gate_walk): gate_min and gate_eval
+// <= 0, gate_idle and gate_walk < 0 keep the value (gate_idle 0 is rejected by the callers).
+void apply_gates(int g[4], int gate_min, int gate_idle, int gate_eval, int gate_walk) {
+  if (gate_min > 0) g[0] = gate_min;
+  if (gate_idle >= 0) g[1] = gate_idle;
+  if (gate_eval > 0) g[2] = gate_eval;
+  if (gate_walk >= 0) g[3] = gate_walk;
+}
+}  // namespace
+
 extern "C" {
 
 int vpt_gpu_film_clear(vpt_gpu_ctx* ctx) {
@@ -1208,10 +1238,14 @@ int vpt_gpu_set_tuning(vpt_gpu_ctx* ctx, int gate_min, int gate_idle, int grid_b
   if (rc) return rc;
   // gate_idle >= 1 is what guarantees progress: with no lane walking, every waiting block runs.
   if (gate_idle == 0) return vpt::set_error(VPT_E_INVALID, "gate_idle must be >= 1 (0 can stall a wavefront)");
-  if (gate_eval > 0) ctx->scene.gate_eval = gate_eval;
-  if (gate_walk >= 0) ctx->scene.gate_walk = gate_walk;
-  if (gate_min > 0) ctx->scene.gate_min = gate_min;
-  if (gate_idle >= 0) ctx->scene.gate_idle = gate_idle;
+  int own[4] = {ctx->scene.gate_min, ctx->scene.gate_idle, ctx->scene.gate_eval, ctx->scene.gate_walk};
+  apply_gates(own, gate_min, gate_idle, gate_eval, gate_walk);
+  ctx->scene.gate_min = own[0];
+  ctx->scene.gate_idle = own[1];
+  ctx->scene.gate_eval = own[2];
+  ctx->scene.gate_walk = own[3];
+  // (the full-launch set follows: existing callers tune every launch of the throughput kernel with this call)
+  apply_gates(ctx->full_gate, gate_min, gate_idle, gate_eval, gate_walk);
   if ((rc = push_scene(ctx))) return rc;
   if (grid_blocks > 0) {
     ctx->grid_blocks = grid_blocks;
@@ -1228,11 +1262,29 @@ int vpt_gpu_set_latency_tuning(vpt_gpu_ctx* ctx, int wave_lanes, int gate_min, i
   int rc = ctx_device(ctx);
   if (rc) return rc;
   if (wave_lanes >= 0) ctx->lat_wave_lanes = wave_lanes;
-  if (gate_min > 0) ctx->lat_gate[0] = gate_min;
-  if (gate_idle >= 0) ctx->lat_gate[1] = gate_idle;
-  if (gate_eval > 0) ctx->lat_gate[2] = gate_eval;
-  if (gate_walk >= 0) ctx->lat_gate[3] = gate_walk;
+  apply_gates(ctx->lat_gate, gate_min, gate_idle, gate_eval, gate_walk);
   return push_scene(ctx);
+}
+
+int vpt_gpu_set_full_tuning(vpt_gpu_ctx* ctx, int gate_min, int gate_idle, int gate_eval, int gate_walk) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "null context");
+  if (gate_idle == 0) return vpt::set_error(VPT_E_INVALID, "gate_idle must be >= 1 (0 can stall a wavefront)");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  apply_gates(ctx->full_gate, gate_min, gate_idle, gate_eval, gate_walk);
+  return push_scene(ctx);
+}
+
+int vpt_gpu_gate_info(const vpt_gpu_ctx* ctx, int set, int* gates, int* last_launch_set) {
+  if (!ctx || set < VPT_GATES_CONTEXT || set > VPT_GATES_FULL)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_gate_info: bad argument");
+  if (gates) {
+    const int own[4] = {ctx->scene.gate_min, ctx->scene.gate_idle, ctx->scene.gate_eval, ctx->scene.gate_walk};
+    const int* g = set == VPT_GATES_CONTEXT ? own : set == VPT_GATES_LATENCY ? ctx->lat_gate : ctx->full_gate;
+    for (int i = 0; i < 4; ++i) gates[i] = g[i];
+  }
+  if (last_launch_set) *last_launch_set = ctx->last_gate_set;
+  return VPT_OK;
 }
 
 int vpt_gpu_set_latency_kernel(vpt_gpu_ctx* ctx, int mode, int ungated) {

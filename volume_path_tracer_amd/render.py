@@ -333,6 +333,18 @@ class Integrator:
         out["cycles_total"] = tot
         return out
 
+    def set_full_tuning(self, gate_min: int = 0, gate_idle: int = -1, gate_eval: int = 0, gate_walk: int = -1):
+        """Gates of full launches alone (set_tuning writes them and the context's); see include/vpt_gpu.h."""
+        capi.check(capi.lib().vpt_gpu_set_full_tuning(self.h, gate_min, gate_idle, gate_eval, gate_walk),
+                   "vpt_gpu_set_full_tuning")
+
+    def gate_info(self, gate_set: int):
+        """((gate_min, gate_idle, gate_eval, gate_walk) of a gate set (capi.VPT_GATES_*), the set the last launch
+        read or -1)."""
+        g, last = (C.c_int * 4)(), C.c_int()
+        capi.check(capi.lib().vpt_gpu_gate_info(self.h, gate_set, g, C.byref(last)), "vpt_gpu_gate_info")
+        return tuple(int(v) for v in g), int(last.value)
+
     def launch_info(self):
         g, b = C.c_int(), C.c_int()
         capi.check(capi.lib().vpt_gpu_launch_info(self.h, C.byref(g), C.byref(b)), "vpt_gpu_launch_info")
