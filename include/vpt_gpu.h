@@ -227,7 +227,8 @@ int vpt_gpu_job_space(const vpt_gpu_ctx* ctx, uint64_t* jobs_per_wave, uint64_t*
  * Concurrency: launches of one context may be in flight on several streams at once.  Each launch
  * takes its own job counter from a ring of 64 per context; a ring slot is reused only after the
  * launch that last held it has completed (the new launch's stream waits on an event), so any number
- * of launches is safe.  Launches that share a film add into it atomically.  The calls that change
+ * of launches is safe.  Launches that share a film add into it atomically (ordered launches -- band launches,
+ * vpt_gpu_render_tiles, among them -- run their film passes one after another instead).  The calls that change
  * context state read by running kernels (vpt_gpu_set_tuning, vpt_gpu_set_rng_mode) and
  * vpt_gpu_film_clear first wait for this context's launches.  One context is driven by one host
  * thread at a time (as the reference's `run` owns its RandomNumberGenerator): a state-changing call
@@ -247,7 +248,8 @@ int vpt_gpu_render_jobs(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count
  *     between launches; C3: 6.4 GB, C5 on one GPU: 102 GB); ordered launches of a context run one at a time
  *     (each waits for the previous one's film pass on its stream).  max_bytes caps the buffer (0 = auto:
  *     3/4 of the device's free memory when it grows): a larger launch is split into consecutive launches,
- *     whole waves at a time where the range allows -- the same film.
+ *     whole waves at a time where the range allows -- the same film.  Band launches (vpt_gpu_render_tiles) use
+ *     the same buffer with a layout of their own, the same event and the same cap.
  *   VPT_FILM_ATOMIC: fp32 atomics as samples complete (the order varies run to run, ≈1e-7 relative).
  * Debug launches (records, events) and feeds always add atomically; so does a launch whose buffer would
  * have to grow while a feed of the context is open.  Growing the buffer frees and allocates device memory,
@@ -259,6 +261,33 @@ int vpt_gpu_set_film_order(vpt_gpu_ctx* ctx, int mode, uint64_t max_bytes);
 /* The film mode, the sample buffer's size and the launches that ran ordered / atomic (feeds not counted). */
 int vpt_gpu_film_order_info(const vpt_gpu_ctx* ctx, int* mode, uint64_t* buffer_bytes, uint64_t* ordered_launches,
                             uint64_t* atomic_launches);
+
+/* A band launch: renders the jobs { (wave_begin + w) * T + t : t in [tile_lo, tile_hi), w in [0, wave_count) } --
+ * wave_count waves (0-based) of a band of consecutive tiles -- asynchronously on `hip_stream`, adding into
+ * `film_device` (NULL = the context's own film).  It is the partition a multi-GPU frame needs to stay bit-exact:
+ * each pixel's samples are added in wave order (w += 1, xyz += imaging_ratio * L, vpt_film_order_kernel's
+ * sequence), so a band rendered from a zero film equals the reference's film on the band's pixels bit for bit,
+ * every other pixel is left untouched, and the films of disjoint bands sum exactly (x + (+0.0) == x).  Every job
+ * keeps its jid and its RNG stream.
+ *   Order and layout: the same-tile order restricted to the band -- the band's tiles by descending cost
+ *     (vpt_gpu_tile_costs, ties as there), each tile's waves consecutively, whatever vpt_gpu_set_job_order says;
+ *     grid size, latency kernel and gate set are chosen from the (tile_hi - tile_lo) * wave_count work items as
+ *     vpt_gpu_render_jobs chooses them from jid_count.  The samples are stored in groups of 64 waves, a pixel's 64
+ *     samples of a group adjacent (the 64 lanes of a wavefront store 768 contiguous bytes), in the context's sample
+ *     buffer: (tile_hi - tile_lo) * ceil(wave_count / 64) * 64 * tile_w*tile_h * 12 bytes.
+ *   Ordered film only: VPT_E_STATE with VPT_FILM_ATOMIC, while a frame is open (vpt_gpu_frame_open), and when the
+ *     sample buffer would have to grow while a feed of the context is open (size it beforehand).  There are no
+ *     records or events variants.
+ *   VPT_E_INVALID: a null context, tile_lo >= tile_hi or tile_hi > T, the pixel RNG mode, 2^32 or more sample
+ *     slots (wave_count rounded up to 64, times max(T, tile_hi - tile_lo)).  wave_count == 0 does nothing (VPT_OK).
+ *   Band launches count as ordered launches (vpt_gpu_film_order_info) and run one at a time with the context's
+ *     other ordered launches (each waits on its stream for the previous one's film pass).  Over max_bytes
+ *     (vpt_gpu_set_film_order) a band launch is split into consecutive blocks of waves, multiples of 64 where the
+ *     cap allows, each with its own film pass in wave order: the same film.  VPT_E_NOMEM when not one wave of the
+ *     band fits.  Apart from the sample buffer nothing is allocated per launch (the band's tile ranks live in a
+ *     buffer of T words allocated with the tile costs), so a launch never waits for a running feed. */
+int vpt_gpu_render_tiles(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t tile_hi, uint64_t wave_begin,
+                         uint64_t wave_count, float* film_device, void* hip_stream);
 
 /* The drop-in's ordered frame (vpt_run.hpp: vpt_gpu::run's film, bit-identical to the reference's).  A feed's jobs
  * arrive in the provider's order and its film is progressive, so its launch adds samples with fp32 atomics; with a

@@ -239,6 +239,7 @@ def lib() -> C.CDLL:
     L.vpt_gpu_job_space.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.vpt_gpu_render_jobs.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
     L.vpt_gpu_render_jobs_records.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
+    L.vpt_gpu_render_tiles.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
     L.vpt_gpu_sync.argtypes = [vp]
     L.vpt_gpu_film_clear.argtypes = [vp]
     L.vpt_gpu_film_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]

@@ -64,6 +64,11 @@ struct FeedLaunch {
   uint64_t* waiting;
   uint32_t* tile_done;  // nullptr unless a staged feed
 };
+// A band launch (vpt_gpu_render_tiles): `waves` waves of the tiles [tile_lo, tile_lo + tiles), their samples in
+// groups of `group` waves (vpt_integrator.h band_slot).
+struct BandLaunch {
+  uint32_t tile_lo, tiles, waves, group;
+};
 }  // namespace vpt
 
 struct vpt_gpu_feed;
@@ -138,6 +143,11 @@ struct vpt_gpu_ctx {
   hipEvent_t samples_done = nullptr;
   bool samples_used = false;
   uint64_t ordered_launches = 0, atomic_launches = 0;  // (vpt_gpu_film_order_info)
+  // Band launches (vpt_gpu_render_tiles): the band's tile ranks (T words, device; allocated with `order`, never per
+  // launch) as last filled for the tiles [band_rank_lo, band_rank_hi) (equal: not filled).  Band launches are
+  // ordered launches, one at a time (samples_done), so the next one may refill it on its stream.
+  uint32_t* band_rank = nullptr;
+  uint32_t band_rank_lo = 0, band_rank_hi = 0;
   // The drop-in's ordered frame (vpt_gpu_frame_open / _finish): its feed launches also store the samples of the
   // frame's tiles [frame_tile_lo, + frame_tiles) from job frame_jid_lo on into the sample buffer above, frame_waves
   // waves of those tiles (0: no frame open); the order pass writes frame_film (device, film_count floats), copied
@@ -194,10 +204,11 @@ namespace vpt::host {
 // vpt_gpu.hip
 int ctx_device(vpt_gpu_ctx* ctx);  // binds the calling thread to the context's device
 // Renders jobs [jid_begin, jid_begin + jid_count) (the launch's kernel variant, grid and job order chosen here);
-// feed != nullptr: the feed's launch (job ids from its ring).
+// feed != nullptr: the feed's launch (job ids from its ring).  band != nullptr: a band launch -- jid_begin is the
+// first wave's first job id, jid_count the band's work items (tiles x waves); ordered film only, no records or events.
 int render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, float* film, float* records, void* stream_ptr,
            vpt_event* events = nullptr, uint64_t event_cap = 0, uint32_t* slot_out = nullptr,
-           const vpt::FeedLaunch* feed = nullptr);
+           const vpt::FeedLaunch* feed = nullptr, const vpt::BandLaunch* band = nullptr);
 // The sample-count channel of a closed feed: each pixel of tile t gains counts_dev[t] (vpt_tile_count_kernel).
 int launch_tile_counts(vpt_gpu_ctx* ctx, float* film, const uint32_t* counts_dev, hipStream_t s);
 // vpt_feed.cpp

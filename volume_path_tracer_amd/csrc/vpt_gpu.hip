@@ -187,6 +187,7 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->scene_lat_dev);
   (void)hipFree(ctx->scene_full_dev);
   (void)hipFree(ctx->order);
+  (void)hipFree(ctx->band_rank);
   (void)hipFree(ctx->perm);
   (void)hipFree(ctx->samples);
   (void)hipFree(ctx->frame_film);
@@ -214,6 +215,9 @@ int rank_tiles(vpt_gpu_ctx* ctx) {
   }
   (void)hipFree(ctx->order);
   ctx->order = d;
+  // (band launches' filtered ranks: the context's one buffer, so that no launch allocates)
+  if (!ctx->band_rank) VPT_HIP(hipMalloc((void**)&ctx->band_rank, T * sizeof(uint32_t)));
+  ctx->band_rank_lo = ctx->band_rank_hi = 0;
   return VPT_OK;
 }
 
@@ -296,19 +300,21 @@ int vpt::host::launch_tile_counts(vpt_gpu_ctx* ctx, float* film, const uint32_t*
 
 int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, float* film, float* records,
                       void* stream_ptr, vpt_event* events, uint64_t event_cap, uint32_t* slot_out,
-                      const vpt::FeedLaunch* feed) {
+                      const vpt::FeedLaunch* feed, const vpt::BandLaunch* band) {
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "render: null context");
   int rc = ctx_device(ctx);
   if (rc) return rc;
   if (jid_count == 0) return VPT_OK;
   if (feed && (ctx->scene.pixel_mode || records || events))
     return vpt::set_error(VPT_E_INVALID, "render: feeds run the reference RNG mode's production kernels only");
+  if (band && (feed || records || events || ctx->scene.pixel_mode || ctx->film_order != VPT_FILM_ORDERED || ctx->frame_waves))
+    return vpt::set_error(VPT_E_INVALID, "render: band launches are ordered production launches of the reference RNG mode");
   // The ordered film: production launches of the reference RNG mode (debug launches and feeds add atomically).
   // A launch whose sample buffer would exceed the cap is rendered as consecutive launches (whole waves where it
   // can); each adds its own waves in order, so the film is the same.
   const uint64_t per_job = (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
   const bool ordered = ctx->film_order == VPT_FILM_ORDERED && !feed && !records && !events && !ctx->scene.pixel_mode;
-  if (ordered) {
+  if (ordered && !band) {  // (vpt_gpu_render_tiles splits its launches itself: by waves)
     const uint64_t max_jobs = std::min<uint64_t>(ordered_cap(ctx, jid_count * per_job) / per_job, 0xffffffffULL);
     if (max_jobs == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one job's samples");
     if (jid_count > max_jobs) {
@@ -401,7 +407,11 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   const bool compact = use_lat && !latency && ctx->compact_every > 0 &&
                        (uint64_t)blocks <= cus * (uint64_t)std::max(0, ctx->compact_per_cu);
   const uint64_t T = ctx->scene.T;
-  if (!feed && ctx->order_mode != VPT_ORDER_JID && jid_begin % T == 0 && jid_count % T == 0 && jid_count < (1ULL << 32)) {
+  if (band) {
+    // the same-tile order restricted to the band (band_job), whatever the context's job order: the sample layout
+    // is built on it
+    if ((rc = ensure_order(ctx))) return rc;
+  } else if (!feed && ctx->order_mode != VPT_ORDER_JID && jid_begin % T == 0 && jid_count % T == 0 && jid_count < (1ULL << 32)) {
     // whole waves: take the jobs in cost order (same jobs, same samples)
     if ((rc = ensure_order(ctx))) return rc;
     const uint32_t n = (uint32_t)(jid_count / T);
@@ -425,16 +435,46 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
     env.order_tail_n = tail;
     env.order_tail_k0 = (n - tail) * (uint32_t)T;
   }
-  if (!feed && ctx->perm && ctx->perm_n == jid_count && !ctx->scene.pixel_mode) env.perm = ctx->perm;
+  if (!feed && !band && ctx->perm && ctx->perm_n == jid_count && !ctx->scene.pixel_mode) env.perm = ctx->perm;
   float* samples = nullptr;
   // (while the drop-in's ordered frame is open its feeds own the sample buffer: other launches add with atomics)
-  if (ordered && !ctx->frame_waves && (rc = ensure_samples(ctx, jid_count * per_job, samples))) return rc;
+  if (band) {
+    const uint64_t bytes = vpt::band_sample_floats(band->tiles, band->waves, ctx->scene.tile_area, band->group) * sizeof(float);
+    if ((rc = ensure_samples(ctx, bytes, samples))) return rc;
+    if (!samples)
+      return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tiles: the sample buffer would have to grow (" +
+                                             std::to_string(bytes >> 20) + " MiB) while a feed of the context is open");
+  } else if (ordered && !ctx->frame_waves && (rc = ensure_samples(ctx, jid_count * per_job, samples))) {
+    return rc;
+  }
   env.samples = samples;
   if (samples) {
     ++ctx->ordered_launches;
     if (ctx->samples_used) VPT_HIP(hipStreamWaitEvent(s, ctx->samples_done, 0));  // the buffer's previous launch
   } else if (!feed) {
     ++ctx->atomic_launches;
+  }
+  if (band) {
+    // The band's tile ranks: the whole frame's are the job order itself; another band's are filtered from it on
+    // the launch's stream -- after the wait above, so after the previous band launch has read the buffer -- unless
+    // the buffer still holds this band's.
+    env.band_rank = ctx->order;
+    if (band->tile_lo != 0 || band->tiles != T) {
+      if (!ctx->band_rank) return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tiles: no tile-rank buffer (its allocation failed)");
+      if (ctx->band_rank_lo != band->tile_lo || ctx->band_rank_hi != band->tile_lo + band->tiles) {
+        hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, band->tile_lo,
+                           band->tile_lo + band->tiles, ctx->band_rank);
+        VPT_HIP(hipGetLastError());
+        ctx->band_rank_lo = band->tile_lo;
+        ctx->band_rank_hi = band->tile_lo + band->tiles;
+      }
+      env.band_rank = ctx->band_rank;
+    }
+    env.band_waves = band->waves;
+    env.band_T = (uint32_t)T;
+    env.band_tile_lo = band->tile_lo;
+    env.band_groups = vpt::band_groups(band->waves, band->group);
+    env.band_group = band->group;
   }
   uint32_t slot = 0;
   if ((rc = take_slot(ctx, s, slot))) return rc;
@@ -462,7 +502,28 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // first slots would leave the fetching slots to finished ones)
   const vpt::DevScene* scene =
       latency || (use_lat && ctx->lat_ungated && !compact) ? ctx->scene_lat_dev : ctx->scene_dev;
-  if (use_lat) {
+  if (band) {  // the Band instantiations of the same kernels, by the same rules
+    if (use_lat) {
+      env.compact_every = (uint32_t)std::max(1, ctx->compact_every);
+      if (compact) {
+        auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true, true, false, true>
+                           : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true, true, false, true>
+                                           : vpt::vpt_integrate_kernel<false, false, false, true, true, false, true>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), vpt::kXchgBytes, s, env, scene, ctx->counters);
+      } else {
+        auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true, false, false, true>
+                           : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true, false, false, true>
+                                           : vpt::vpt_integrate_kernel<false, false, false, true, false, false, true>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
+      }
+    } else {
+      auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, true>
+                         : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, true>
+                                         : vpt::vpt_integrate_kernel<false, false, false, false, false, false, true>;
+      if (scene == ctx->scene_dev) scene = ctx->scene_full_dev;  // (the full-launch gates, as below)
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
+    }
+  } else if (use_lat) {
     env.compact_every = (uint32_t)std::max(1, ctx->compact_every);
     if (compact) {
       auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true, true>
@@ -494,7 +555,14 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
                        : scene == ctx->scene_lat_dev ? VPT_GATES_LATENCY : VPT_GATES_CONTEXT;  // (vpt_gpu_gate_info)
   VPT_HIP(hipGetLastError());
   const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
-  if (samples) {  // the film, pixel by pixel in wave order (sample counts included)
+  if (band) {  // the film's pixels of the band, in wave order (sample counts included)
+    const uint32_t chunks = (ctx->scene.tile_area + 63u) / 64u;
+    hipLaunchKernelGGL(vpt::vpt_band_order_kernel, dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev, env.film,
+                       samples, band->tile_lo, band->waves, env.band_groups, band->group);
+    VPT_HIP(hipGetLastError());
+    VPT_HIP(hipEventRecord(ctx->samples_done, s));
+    ctx->samples_used = true;
+  } else if (samples) {  // the film, pixel by pixel in wave order (sample counts included)
     const uint64_t threads = ctx->scene.T * (uint64_t)ctx->scene.tile_area;
     hipLaunchKernelGGL(vpt::vpt_film_order_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
                        ctx->scene_dev, env.film, samples, jid_begin, jid_count);
@@ -808,6 +876,42 @@ int vpt_gpu_job_space(const vpt_gpu_ctx* ctx, uint64_t* jobs_per_wave, uint64_t*
 int vpt_gpu_render_jobs(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, float* film_device,
                         void* hip_stream) {
   return render(ctx, jid_begin, jid_count, film_device, nullptr, hip_stream);
+}
+
+int vpt_gpu_render_tiles(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t tile_hi, uint64_t wave_begin, uint64_t wave_count,
+                         float* film_device, void* hip_stream) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tiles: null context");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  const uint64_t T = ctx->scene.T;
+  if (tile_lo >= tile_hi || tile_hi > T) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tiles: bad tile range");
+  if (ctx->scene.pixel_mode)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tiles: band launches run the reference RNG mode");
+  // 32-bit work items, job offsets (w * T + tile) and wave slots (tiles x waves padded to whole groups)
+  const uint64_t B = tile_hi - tile_lo, G = vpt::kBandGroup;
+  if (wave_count >= (1ULL << 32) || (wave_count + G - 1) / G * G * std::max(B, T) >= (1ULL << 32) ||
+      wave_begin > (UINT64_MAX / T) - wave_count)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tiles: 2^32 or more sample slots (render fewer waves per call)");
+  if (ctx->film_order != VPT_FILM_ORDERED)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tiles: band launches need the ordered film "
+                                       "(vpt_gpu_set_film_order: VPT_FILM_ORDERED)");
+  if (ctx->frame_waves)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tiles: a frame is open (vpt_gpu_frame_open owns the sample buffer)");
+  if (wave_count == 0) return VPT_OK;
+  // The cap (vpt_gpu_set_film_order's max_bytes, else what the device has free): consecutive blocks of waves, each
+  // with its own film pass, in wave order -- the same film.  Whole groups of 64 waves where the cap allows; below
+  // that a block's group is as wide as the block, so its buffer is no larger than its waves' samples.
+  const uint64_t per_wave = B * (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
+  const uint64_t max_waves = ordered_cap(ctx, (wave_count + G - 1) / G * G * per_wave) / per_wave;
+  if (max_waves == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one wave of the band's samples");
+  const uint64_t chunk = max_waves >= G ? max_waves / G * G : max_waves;
+  for (uint64_t b = 0; b < wave_count; b += chunk) {
+    const uint64_t n = std::min(chunk, wave_count - b);
+    const vpt::BandLaunch band{tile_lo, (uint32_t)B, (uint32_t)n, (uint32_t)(max_waves >= G ? G : n)};
+    if ((rc = render(ctx, (wave_begin + b) * T, B * n, film_device, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, &band)))
+      return rc;
+  }
+  return VPT_OK;
 }
 
 int vpt_gpu_render_jobs_records(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, float* film_device,

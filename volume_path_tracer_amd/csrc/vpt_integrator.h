@@ -1130,6 +1130,33 @@ __host__ __device__ __forceinline__ uint64_t ordered_job(uint32_t k, uint32_t T,
   return (uint64_t)(tail_k0 / T + w) * T + order[i];
 }
 
+// A band launch (vpt_gpu_render_tiles): `waves` waves of the tiles [tile_lo, tile_hi), B of them, in the same-tile
+// order restricted to the band -- item k of B * waves is wave k % waves (relative to the launch's first) of the
+// band's k / waves-th tile by descending cost (band_rank: the tile ranks filtered to the band, ties as there).
+// Returns the job's offset from the launch's first job id, w * T + tile.
+constexpr uint32_t kBandGroup = 64;  // the sample layout's group width: the lanes of a wavefront
+__host__ __device__ __forceinline__ uint64_t band_job(uint64_t k, uint32_t waves, uint32_t T, const uint32_t* band_rank) {
+  const uint64_t i = k / waves;
+  const uint32_t w = (uint32_t)(k - i * waves);
+  return (uint64_t)w * T + band_rank[i];
+}
+// A band launch's samples, lane-adjacent: waves are cut into groups of G (kBandGroup; fewer only when a capped
+// launch is shorter than that), and the float offset of wave w (relative to the launch's first) of the band's
+// tb-th tile (tile - tile_lo) at local pixel q is
+//   ((((tb * groups + w / G) * tile_area + q) * G) + w % G) * 3,   groups = ceil(waves / G):
+// the 64 lanes of a same-tile wavefront that finish pixel q store 64 x 12 adjacent bytes.  The buffer holds
+// band_sample_floats (the last group is padded to G waves).
+__host__ __device__ __forceinline__ uint32_t band_groups(uint32_t waves, uint32_t G) { return (waves + G - 1) / G; }
+__host__ __device__ __forceinline__ uint64_t band_slot(uint32_t tb, uint32_t w, uint32_t q, uint32_t groups,
+                                                       uint32_t tile_area, uint32_t G) {
+  const uint32_t g = w / G;
+  return (((((uint64_t)tb * groups + g) * tile_area + q) * G) + (w - g * G)) * 3;
+}
+__host__ __device__ __forceinline__ uint64_t band_sample_floats(uint32_t tiles, uint32_t waves, uint32_t tile_area,
+                                                                uint32_t G) {
+  return (uint64_t)tiles * band_groups(waves, G) * tile_area * G * 3;
+}
+
 // ------------------------------------------------------------------------------------------------
 // One iteration of the lane loop.  Env supplies fetch_job(uint64_t& item, wave_lanes) -> bool, jid_begin, the
 // job order (order == nullptr: item k is job jid_begin + k; else ordered_job()),

@@ -86,6 +86,16 @@ struct KernelArgs {
   uint64_t frame_slots;
   uint32_t frame_tile_lo;
   uint32_t frame_tiles;
+  // A band launch (vpt_gpu_render_tiles; the kernels' Band instantiations only): item k of jid_count = tiles x
+  // band_waves is job band_job(k, ...) of the band's tiles by descending cost (band_rank), and its samples are
+  // stored lane-adjacent (band_slot: groups of band_group waves, band_groups of them per tile) for
+  // vpt_band_order_kernel.
+  const uint32_t* band_rank;
+  uint32_t band_waves;
+  uint32_t band_T;
+  uint32_t band_tile_lo;
+  uint32_t band_groups;
+  uint32_t band_group;
 };
 typedef const __attribute__((address_space(4))) KernelArgs* ArgsPtr;
 // This workgroup's event counters and (VPT_PROFILE builds) section cycles; the temperature kernel's LDS copy of
@@ -103,9 +113,12 @@ __shared__ uint32_t g_film_rank[kBlockThreads];
 // arguments are read where they are used, through an opaque pointer to the kernel's argument segment (scalar
 // loads, as the scene's constants are, see ScenePtr): loads the optimiser cannot hoist, so no argument stays live
 // in SGPRs across the state-machine loop (they spilled to VGPR lanes: v_readlane / v_writelane in every block).
-template <bool RegCold, bool Feed = false>
+// Band: a band launch's (vpt_gpu_render_tiles): its own item -> job mapping and sample layout, read in fetch_job,
+// job_start and film_add only; every other launch compiles them out.
+template <bool RegCold, bool Feed = false, bool Band = false>
 struct KernelEnvT {
   static_assert(!(RegCold && Feed), "feeds run the throughput kernels only");
+  static_assert(!(Band && Feed), "band launches are no feeds");
   __device__ __forceinline__ ArgsPtr args() const {
     ArgsPtr p = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();  // (KernelArgs is the first argument: offset 0)
     asm volatile("" : "+s"(p));
@@ -231,7 +244,10 @@ struct KernelEnvT {
     if ((int32_t)__lane_id() >= wave_lanes) return false;
     unsigned long long v = atomicAdd(args()->job_counter, 1ULL);
     if (v >= args()->jid_count) return 0;
-    j = v;
+    if constexpr (Band)  // (the launch passes no order and no permutation: j is the job's offset from jid_begin)
+      j = band_job(v, args()->band_waves, args()->band_T, args()->band_rank);
+    else
+      j = v;
     return 1;
   }
   // Feed mode: the lane reserves item k (one atomic on the launch's counter) and keeps it in its cold
@@ -317,9 +333,17 @@ struct KernelEnvT {
     return -1;
   }
   // A job starts (its id jid): with an ordered frame, a feed lane keeps the address of the job's samples in its cold
-  // state (item_lo / item_hi: free once the job is read).  Other launches: nothing.
+  // state (item_lo / item_hi: free once the job is read).  A band launch's lane keeps there the address of its
+  // job's first sample (band_slot at pixel 0; item_lo holds the job's offset w * T + tile from jid_begin, < 2^32).
+  // Other launches: nothing.
   __device__ __forceinline__ void job_start(const DevScene& S, LaneCold& lc, uint64_t jid) {
-    if constexpr (Feed) {
+    if constexpr (Band) {
+      (void)jid;
+      const uint32_t T = args()->band_T, w = lc.item_lo / T, tb = lc.item_lo - w * T - args()->band_tile_lo;
+      const uint64_t a = (uint64_t)(args()->samples + band_slot(tb, w, 0, args()->band_groups, S.tile_area, args()->band_group));
+      lc.item_lo = (uint32_t)a;
+      lc.item_hi = (uint32_t)(a >> 32);
+    } else if constexpr (Feed) {
       if (float* const frame = args()->frame) {
         const uint64_t w = jid / S.T;
         const uint32_t tt = (uint32_t)(jid - w * S.T) - args()->frame_tile_lo;  // (wraps below the band: > tiles)
@@ -359,12 +383,25 @@ struct KernelEnvT {
   // than regrouped through the wavefront as the atomics are (C3 336.1 vs 337.9 ms, C4 81.2 vs 84.2; r06f,
   // profiles/r06f_ordered_direct_and_ray_gate_ab.txt).  (The early return and film_commit's store branch stay as
   // measured: equivalent rewrites of these lines moved the temperature kernel from 0 to 12 bytes of spills.)
+  //
+  // A band launch stores from the lane too, at its job's address (job_start) + pixel * band_group * 3 floats: under
+  // the same-tile order the wavefront's lanes are consecutive waves of one tile, whose samples of a pixel are adjacent.
   __device__ __forceinline__ bool film_regroup(const DevScene& S) const {
+    if constexpr (Band) return false;
     if (args()->samples) return false;
     return !RegCold && (args()->samples != nullptr || (uint64_t)S.W * (uint64_t)S.H < (1ULL << 26));  // (index << 6 | lane fits 32 bits)
   }
   __device__ __forceinline__ void film_add(const DevScene& S, const Lane& ln, int32_t px, int32_t py, int32_t rw) {
     const LaneCold& lc = cold();
+    if constexpr (Band) {
+      (void)ln;
+      float* s = reinterpret_cast<float*>(((uint64_t)lc.item_hi << 32) | lc.item_lo) +
+                 (uint64_t)(uint32_t)((py - lc.y0) * rw + (px - lc.x0)) * (args()->band_group * 3u);
+      s[0] = lc.L[0];
+      s[1] = lc.L[1];
+      s[2] = lc.L[2];
+      return;
+    }
     if constexpr (Feed) {  // the ordered frame's copy of the sample (the film's atomics below stay: the progressive film)
       const uint64_t a = ((uint64_t)lc.item_hi << 32) | lc.item_lo;
       if (args()->frame && a) {
@@ -511,8 +548,8 @@ __device__ __forceinline__ void xchg_unpack(Lane& ln, LaneCold& lc, const uint32
 // Dynamic LDS of the compacting kernel: [kXWords / 4][kBlockThreads] uint4 (61 440 B).
 constexpr size_t kXchgBytes = (size_t)kXWords * kBlockThreads * sizeof(uint32_t);
 
-template <bool HasTemp, bool Runs>
-__device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc, KernelEnvT<true>& env) {
+template <bool HasTemp, bool Runs, class Env>
+__device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc, Env& env) {
   extern __shared__ uint4 g_xchg[];
   __shared__ int32_t cnt[8];  // per wavefront: walking paths, other live paths
   const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -571,7 +608,7 @@ __device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc
 }
 
 // counters[] order = vpt_counters field order
-template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false>
+template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false>
 __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT : (Debug ? VPT_WAVES_SLOW : (HasTemp ? VPT_WAVES_TEMP : VPT_WAVES_FAST)))) void vpt_integrate_kernel(KernelArgs args, const DevScene* scene,
                                                                        unsigned long long* counters) {
   (void)args;  // read through KernelEnvT::args()
@@ -587,7 +624,8 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
   __syncthreads();
   if (threadIdx.x % 64 == 0) g_wg_prof[PT_COUNT + threadIdx.x / 64] = clock64();
 #endif
-  KernelEnvT<Lat, Feed> env;
+  static_assert(!(Band && Debug), "band launches have no records or events");
+  KernelEnvT<Lat, Feed, Band> env;
   env.reg_cold = nullptr;
   Lane ln;
   lane_init(ln);
@@ -723,6 +761,110 @@ __global__ void vpt_frame_order_kernel(const DevScene* scene, float* film, const
     a.z = a.z + r * s[2];
   }
   *f = a;
+}
+
+// A band launch's tile ranks (vpt_gpu_render_tiles): `order` (the T tiles by descending cost) filtered to the tiles
+// [lo, hi), in the same sequence, into out[0 .. hi - lo).  One block: every 256 entries, a wavefront ranks its
+// band tiles with a ballot and the block's four counts give each wavefront its base.
+__global__ __launch_bounds__(256) void vpt_band_rank_kernel(const uint32_t* order, uint32_t T, uint32_t lo, uint32_t hi,
+                                                            uint32_t* out) {
+  __shared__ uint32_t cnt[4];
+  const uint32_t wave = threadIdx.x >> 6;
+  uint32_t base = 0;
+  for (uint32_t i0 = 0; i0 < T; i0 += 256) {  // (uniform)
+    const uint32_t i = i0 + threadIdx.x;
+    const uint32_t t = i < T ? order[i] : 0u;
+    const bool in = i < T && t >= lo && t < hi;
+    const uint64_t m = __builtin_amdgcn_ballot_w64(in);
+    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if ((threadIdx.x & 63u) == 0) cnt[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < 4; ++v) {
+      const uint32_t c = cnt[v];
+      if (v < wave) before += c;
+      total += c;
+    }
+    // (order is a permutation of the tiles, so at most hi - lo <= T entries are written)
+    if (in && base + before + r < hi - lo) out[base + before + r] = t;
+    base += total;
+    __syncthreads();  // cnt is rewritten by the next 256
+  }
+}
+
+// A band launch's film pass (vpt_gpu_render_tiles): adds the samples of `waves` waves of the band's tiles into the
+// film pixel by pixel in wave order -- w += 1, xyz += imaging_ratio * L per sample (worker.cpp:203-204), exactly
+// vpt_film_order_kernel's sequence -- and touches no pixel outside the band.  The samples lie lane-adjacent
+// (band_slot): a pixel's G waves of a group are one run of G * 12 bytes, the next pixel's run follows it.  A thread
+// per pixel reading its own run would have a wavefront load 64 addresses 768 B apart per instruction, so the runs
+// go through LDS: a block is one wavefront that owns up to 64 pixels of a tile; per group it stages
+// kBandStageWaves waves of its pixels at a time -- per pixel 192 contiguous bytes, fetched as 16-B loads by
+// consecutive lanes -- and thread p then walks pixel p's samples from LDS in wave order.  A pixel's LDS row is
+// 49 words, an odd stride, so the 32 lanes of a ds_read_b32 group hit 32 different banks (48 would put every
+// row on banks 0, 16).  12.25 KiB per block: 13 wavefronts per CU by LDS (160 KiB), each with 12 KiB of loads in
+// flight -- about the 64 KiB per CU that HBM's bandwidth-latency product asks for, twice over.  Groups narrower
+// than a multiple of 4 waves (a capped launch's, G < 64) leave the runs unaligned for 16-B loads and are staged
+// with 4-B ones.  The last group's padding and ragged tiles' missing pixels are staged (the buffer holds them)
+// but never added.
+constexpr uint32_t kBandStageWaves = 16;
+constexpr uint32_t kBandStageStride = kBandStageWaves * 3 + 1;
+__global__ __launch_bounds__(64) void vpt_band_order_kernel(const DevScene* scene, float* film, const float* samples,
+                                                            uint32_t tile_lo, uint32_t waves, uint32_t groups, uint32_t G) {
+  __shared__ float stage[64 * kBandStageStride];
+  const DevScene& S = *scene;
+  const uint32_t area = S.tile_area, chunks = (area + 63u) / 64u;
+  const uint32_t tb = blockIdx.x / chunks, q0 = (blockIdx.x - tb * chunks) * 64u;
+  const uint32_t np = min(64u, area - q0);  // the block's pixels q0 .. q0 + np of the tile
+  const uint32_t t = tile_lo + tb, q = q0 + threadIdx.x;
+  const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
+  const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
+  bool mine = threadIdx.x < np && (int32_t)q < rw * rh;
+  const int32_t yl = (int32_t)q / rw, px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
+  if (S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) mine = false;  // (no sample: worker.cpp:113-116)
+  float4* const f = reinterpret_cast<float4*>(film) + ((uint64_t)py * (uint64_t)S.W + (uint64_t)px);
+  float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (mine) a = *f;
+  const float r = S.imaging_ratio;
+  const bool vec = (G & 3u) == 0;
+  const float* const row = stage + threadIdx.x * kBandStageStride;
+  for (uint32_t g = 0; g < groups; ++g) {  // (every loop bound below is uniform: the barriers are too)
+    const uint32_t gw = min(G, waves - g * G);  // the group's waves
+    const float* const base = samples + (((uint64_t)tb * groups + g) * area + q0) * G * 3u;
+    for (uint32_t c0 = 0; c0 < gw; c0 += kBandStageWaves) {
+      const uint32_t cw = min(kBandStageWaves, gw - c0);  // waves to add
+      if (vec) {
+        const uint32_t per = min(kBandStageWaves, G - c0) * 3u / 4u;  // 16-B loads per pixel (the layout's waves)
+#pragma unroll 4
+        for (uint32_t i = threadIdx.x; i < np * per; i += 64u) {
+          const uint32_t p = i / per, k = i - p * per;
+          const float4 v = *reinterpret_cast<const float4*>(base + (uint64_t)p * G * 3u + c0 * 3u + k * 4u);
+          float* d = stage + p * kBandStageStride + k * 4u;
+          d[0] = v.x;
+          d[1] = v.y;
+          d[2] = v.z;
+          d[3] = v.w;
+        }
+      } else {
+        const uint32_t per = cw * 3u;
+#pragma unroll 4
+        for (uint32_t i = threadIdx.x; i < np * per; i += 64u) {
+          const uint32_t p = i / per, k = i - p * per;
+          stage[p * kBandStageStride + k] = base[(uint64_t)p * G * 3u + c0 * 3u + k];
+        }
+      }
+      __syncthreads();
+      if (mine)
+        for (uint32_t k = 0; k < cw; ++k) {  // (in wave order, never reduced across waves)
+          a.w = a.w + 1.0f;
+          a.x = a.x + r * row[3 * k];
+          a.y = a.y + r * row[3 * k + 1];
+          a.z = a.z + r * row[3 * k + 2];
+        }
+      __syncthreads();  // the stage is rewritten
+    }
+  }
+  if (mine) *f = a;
 }
 
 // The drop-in's seed recovery (include/vpt_run.hpp rng_seed): the reference's RandomNumberGenerator keeps its u32

@@ -40,8 +40,9 @@ class TileProvider:
         self._lock = threading.Lock()
         self._start = time.monotonic()
 
-    # token next() without per-tile wave gating: on the GPU the film adds are atomics, so two
-    # waves of a tile may be in flight together (the reference serialises them, tile_provider.cpp:40-60).
+    # token next() without per-tile wave gating: on the GPU two waves of a tile may be in flight together
+    # (the reference serialises them, tile_provider.cpp:40-60) -- the ordered film (the default) stores every
+    # sample and adds them pixel by pixel in wave order after the launch; VPT_FILM_ATOMIC adds with fp32 atomics.
     def next_batch(self, max_jobs: int):
         """Reserve up to max_jobs consecutive job ids: (jid_begin, count), count 0 when done."""
         with self._lock:
@@ -182,6 +183,22 @@ class Integrator:
     def render_waves(self, first_wave: int, num_waves: int, film=None, stream=None):
         """Waves are 1-based (tile_provider.cpp:30): wave w covers jids [(w-1)*T, w*T)."""
         self.render_jobs((first_wave - 1) * self.jobs_per_wave, num_waves * self.jobs_per_wave, film, None, stream)
+
+    def render_tiles(self, tile_lo: int, tile_hi: int, first_wave: int, num_waves: int, film=None, stream=None):
+        """Asynchronously render waves first_wave .. first_wave + num_waves - 1 (1-based, as render_waves) of the
+        tiles [tile_lo, tile_hi) into `film` (default: own) with one band launch (vpt_gpu_render_tiles): the band's
+        pixels receive their samples in wave order, bit for bit the reference's film, and no other pixel is
+        touched -- so films of disjoint bands sum exactly.  Needs the ordered film (the default)."""
+        film = self.film if film is None else film
+        assert film.is_cuda and film.dtype == self.torch.float32 and film.is_contiguous()
+        assert film.numel() == self.cfg.height * self.cfg.width * 4
+        if first_wave < 1 or num_waves < 0:
+            raise ValueError("render_tiles: waves are 1-based, num_waves >= 0")
+        if not (0 <= tile_lo <= 0xFFFFFFFF and 0 <= tile_hi <= 0xFFFFFFFF):
+            raise ValueError("render_tiles: tile indices are 32-bit")
+        capi.check(capi.lib().vpt_gpu_render_tiles(self.h, int(tile_lo), int(tile_hi), int(first_wave) - 1,
+                                                   int(num_waves), C.c_void_p(film.data_ptr()),
+                                                   C.c_void_p(self.stream_handle(stream))), "vpt_gpu_render_tiles")
 
     def trace_jobs(self, jid_begin: int, jid_count: int, capacity: int = 1 << 20, film=None, stream=None):
         """Render jobs and return their Logger events (worker.cpp:16-48) as a numpy array of
