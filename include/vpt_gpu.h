@@ -289,6 +289,85 @@ int vpt_gpu_film_order_info(const vpt_gpu_ctx* ctx, int* mode, uint64_t* buffer_
 int vpt_gpu_render_tiles(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t tile_hi, uint64_t wave_begin,
                          uint64_t wave_count, float* film_device, void* hip_stream);
 
+/* Adaptive sampling.  Four calls: a second-moment plane the ordered film passes keep beside the film, a launch
+ * over an arbitrary list of tiles, a per-tile error estimate, and a driver that renders every tile until its
+ * estimate is below a target.  A tile stopped after k waves holds exactly the reference's film of that tile after
+ * k waves: every job keeps its jid and RNG stream, so adaptive sampling takes a per-tile prefix of the reference's
+ * sample set and never leaves it.  Out of scope: the drop-in vpt_gpu::run (the reference's TileProvider dictates
+ * its jobs), the multi-GPU modes, feeds, and the pixel RNG mode.
+ *
+ * The moment plane: `m2_device` is a device float[H][W] owned by the caller; NULL detaches.  While a plane is
+ * attached every ordered production launch (vpt_gpu_render_jobs, vpt_gpu_render_tiles, vpt_gpu_render_tile_list,
+ * the launches they are split into under max_bytes included) also does, for each sample it adds to a pixel, after
+ * the four adds of the film and in the same wave order,
+ *     y = imaging_ratio * L.y;   m2 = m2 + y * y          (fp32, not contracted)
+ * reading and writing the plane once per pixel per pass.  Pixels that receive no sample (outside the band or list,
+ * a ragged tile's padding, every other pixel in single-pixel mode) are not touched.  VPT_E_STATE with
+ * VPT_FILM_ATOMIC and while a frame is open.  With a plane attached a launch that would add with film atomics --
+ * a debug launch (records, events), the pixel RNG mode, VPT_FILM_ATOMIC, an open frame, a sample buffer that would
+ * have to grow while a feed of the context is open -- fails with VPT_E_STATE instead of leaving the plane behind
+ * the film.  Feeds are unaffected and never write the plane.  Takes effect at the next launch. */
+int vpt_gpu_set_film_moments(vpt_gpu_ctx* ctx, float* m2_device);
+
+/* A tile-list launch: vpt_gpu_render_tiles for the tiles tiles[0..n) (a host array, strictly ascending, every entry
+ * < T) instead of [tile_lo, tile_hi): renders the jobs (wave_begin + w) * T + tiles[i], w in [0, wave_count), adds
+ * each pixel's samples in wave order and touches no pixel outside the listed tiles.  Order: the list's tiles by
+ * descending cost (ties as in vpt_gpu_tile_costs' ranks), each tile's waves consecutively; the samples lie as a
+ * band's, the tile's index in the list in place of its offset in the band (n * ceil(wave_count / 64) * 64 *
+ * tile_w*tile_h * 12 bytes).  The same rules as band launches: ordered film only, no open frame (VPT_E_STATE), the
+ * reference RNG mode (VPT_E_INVALID), split by waves under max_bytes, VPT_E_NOMEM when not one wave fits, counted
+ * as ordered launches; wave_count == 0 or n == 0 does nothing (VPT_OK).  Also VPT_E_INVALID for an unsorted or
+ * duplicated list or an entry >= T, and VPT_E_STATE while a feed of the context is launched and not closed: the
+ * list is uploaded by the call (two buffers of T words allocated with the tile costs; the call first waits for the
+ * context's previous ordered launch, which may still read them), and an upload must not wait for a launch that
+ * holds the device.  A list equal to the previous call's is not uploaded again. */
+int vpt_gpu_render_tile_list(vpt_gpu_ctx* ctx, const uint32_t* tiles, uint32_t n, uint64_t wave_begin,
+                             uint64_t wave_count, float* film_device, void* hip_stream);
+
+/* Per-tile error estimates of a film and its moment plane (film_device NULL = the context's own film), synchronous:
+ * launched on `hip_stream`, err_T_host[t] is valid on return.  Everything is fp32, in exactly this order.  Pixel q
+ * of tile t (q = y_local * rect_w + x_local) is counted if it lies in the image, is the single pixel when that
+ * mode is on, and n = film.w >= 2; a counted pixel has
+ *     mean = film.y / n;  ex2 = m2 / n;  v = ex2 - mean * mean, 0 unless v > 0;  se = sqrtf(v / (n - 1.0f))
+ * and any other pixel se = mean = +0.0.  Both arrays, indexed by q and padded with +0.0 to P, the power of two >=
+ * tile_w*tile_h, are reduced by the tree: for h = P/2, P/4, .., 1: a[i] = a[i] + a[i + h], i < h.  Then
+ *     err_t = se[0] / (mean[0] + abs_floor * (float)cnt)      (cnt = counted pixels; err_t = 0 when cnt == 0)
+ * -- the tile's mean standard error of Y relative to its mean Y, abs_floor keeping dark tiles finite.  Division and
+ * square root are correctly rounded.  VPT_E_INVALID when abs_floor <= 0, when m2_device or err_T_host is null, and
+ * for tiles of more than 8192 pixels (the tree is reduced in LDS); VPT_E_STATE while a feed of the context is
+ * open. */
+int vpt_gpu_tile_errors(vpt_gpu_ctx* ctx, const float* film_device, const float* m2_device, float abs_floor,
+                        float* err_T_host, void* hip_stream);
+
+/* The adaptive driver, synchronous.  film_device (NULL = the context's film) and m2_device start as zeros: the
+ * caller zeroes them.  The call attaches m2_device and restores the previous attachment on return.
+ *   Round 0 renders waves [0, min_waves) of every tile.  Every later round computes vpt_gpu_tile_errors, keeps the
+ *   tiles of the previous round's list with err_t > target_error that are below max_waves, and renders the next
+ *   min(step_waves, max_waves - done) waves of exactly those with one list launch; it stops when the list is empty.
+ *   A tile that leaves the list never returns, so every listed tile has the same wave count and the result is a
+ *   per-tile prefix of the uniform frame's samples.  target_error == 0 stops no tile -- not even a black one, whose
+ *   estimate is exactly 0 -- so every tile gets max_waves and the film is the uniform frame's, byte for byte.
+ * waves_T_host[t]: the waves tile t received.  err_T_host[t]: its error in the returned film (a last
+ * vpt_gpu_tile_errors call follows the last round).  out (may be NULL): rounds (round 0 included), tiles_at_max,
+ * jobs_rendered (the sum of waves_T_host), jobs_uniform = max_waves * T, max_error.
+ * VPT_E_INVALID: a null argument, min_waves < 2, step_waves == 0, max_waves < min_waves, target_error < 0 or NaN,
+ * abs_floor <= 0.  Otherwise the errors of the calls above.
+ * Caveat, the usual one of adaptive sampling: a stopping rule fed by the samples it stops biases the estimate
+ * slightly (tiles whose first samples happen to agree stop early).  min_waves is the guard against it. */
+typedef struct vpt_adaptive_params {
+  float target_error, abs_floor;
+  uint32_t min_waves, step_waves, max_waves;
+} vpt_adaptive_params;
+
+typedef struct vpt_adaptive_result {
+  uint32_t rounds, tiles_at_max;
+  uint64_t jobs_rendered, jobs_uniform;
+  float max_error;
+} vpt_adaptive_result;
+
+int vpt_gpu_render_adaptive(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p, float* film_device, float* m2_device,
+                            uint32_t* waves_T_host, float* err_T_host, vpt_adaptive_result* out, void* hip_stream);
+
 /* The drop-in's ordered frame (vpt_run.hpp: vpt_gpu::run's film, bit-identical to the reference's).  A feed's jobs
  * arrive in the provider's order and its film is progressive, so its launch adds samples with fp32 atomics; with a
  * frame open, the context's feed launches also store the samples of the jobs of tiles [tile_lo, tile_hi) in waves

@@ -6,7 +6,10 @@ convert the film to 8-bit sRGB (film_to_image) and save a PNG.
 
 ``--synthetic cloud|constant|fire[:N]`` replaces the volume file by a generated stand-in (the
 reference's volumes are not shipped).  ``--spp`` overrides num_waves; ``--size WxH`` overrides
-output_size.  Exits 1 on a fatal error, like vptFATAL.
+output_size.  ``--adaptive ERR`` renders until every tile's error estimate is at most ERR
+(render.render_adaptive): ``--spp`` becomes the cap, ``--min-spp`` / ``--spp-step`` the first round and
+the later rounds' waves, ``--waves-out`` saves the per-tile wave map.  Exits 1 on a fatal error, like
+vptFATAL.
 """
 from __future__ import annotations
 
@@ -37,10 +40,15 @@ def main(argv=None) -> int:
     ap.add_argument("--event-log", default=None,
                     help="write the Logger event log (log.csv format) of the first --event-jobs jobs")
     ap.add_argument("--event-jobs", type=int, default=1)
+    ap.add_argument("--adaptive", type=float, default=None, metavar="ERR",
+                    help="adaptive sampling: render each tile until its error estimate is <= ERR (--spp is the cap)")
+    ap.add_argument("--min-spp", type=int, default=64, help="adaptive: waves of the first round")
+    ap.add_argument("--spp-step", type=int, default=64, help="adaptive: waves per later round")
+    ap.add_argument("--waves-out", default=None, help="adaptive: save the per-tile wave map (.npy, uint32[T])")
     args = ap.parse_args(argv)
 
     from . import image, traces, volumes
-    from .render import Integrator, TileProvider, run
+    from .render import Integrator, TileProvider, render_adaptive, run
     from .scenes import SynthGrid, read_configuration
 
     try:
@@ -65,13 +73,26 @@ def main(argv=None) -> int:
             print(f"TempMin: {float(temp.leaf_values.min())}, TempMax: {float(temp.leaf_values.max())}")
 
         it = Integrator(cfg, dens, temp, device=args.device)
-        tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
-        tp.reset_eta()
         t0 = time.perf_counter()
-        film = run(cfg, it, tp, batch_jobs=args.batch_jobs)
-        ms = (time.perf_counter() - t0) * 1e3
-        print(f"[vpt] Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
-              file=sys.stderr)
+        if args.adaptive is not None:
+            film, waves, err, info = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
+                                                     step_waves=args.spp_step, max_waves=cfg.num_waves)
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] Adaptive rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, target {args.adaptive:g}, "
+                  f"{int(waves.min())}-{int(waves.max())} spp): {info['jobs_rendered']} of {info['jobs_uniform']} jobs "
+                  f"({info['jobs_rendered'] / info['jobs_uniform']:.3f}), {info['rounds']} rounds, "
+                  f"{info['tiles_at_max']} tiles at the cap, max tile error {info['max_error']:.4g}", file=sys.stderr)
+            if args.waves_out:
+                import numpy as np
+
+                np.save(args.waves_out, waves)
+        else:
+            tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
+            tp.reset_eta()
+            film = run(cfg, it, tp, batch_jobs=args.batch_jobs)
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
+                  file=sys.stderr)
         if args.event_log:
             scratch = it.torch.zeros_like(it.film)  # the traced jobs are not part of the image
             traces.write_event_log(it.trace_jobs(0, args.event_jobs, film=scratch), args.event_log)

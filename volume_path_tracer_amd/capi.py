@@ -88,6 +88,21 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class AdaptiveParams(C.Structure):
+    """vpt_adaptive_params (vpt_gpu_render_adaptive)."""
+    _fields_ = [("target_error", C.c_float), ("abs_floor", C.c_float),
+                ("min_waves", C.c_uint32), ("step_waves", C.c_uint32), ("max_waves", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):
+    """vpt_adaptive_result."""
+    _fields_ = [("rounds", C.c_uint32), ("tiles_at_max", C.c_uint32),
+                ("jobs_rendered", C.c_uint64), ("jobs_uniform", C.c_uint64), ("max_error", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {n: (float if n == "max_error" else int)(getattr(self, n)) for n, _ in self._fields_}
+
+
 # vpt_event (include/vpt_gpu.h): one Logger line (src/worker.cpp:16-48)
 EVENT_DTYPE = np.dtype([("jid", "<u8"), ("pixel", "<u4"), ("seq", "<u4"), ("type", "<u4"), ("v", "<f4", (7,))])
 assert EVENT_DTYPE.itemsize == 48
@@ -240,6 +255,12 @@ def lib() -> C.CDLL:
     L.vpt_gpu_render_jobs.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
     L.vpt_gpu_render_jobs_records.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
     L.vpt_gpu_render_tiles.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
+    if hasattr(L, "vpt_gpu_render_adaptive"):  # (older builds in A/B runs lack the adaptive calls)
+        L.vpt_gpu_set_film_moments.argtypes = [vp, vp]
+        L.vpt_gpu_render_tile_list.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_uint64, vp, vp]
+        L.vpt_gpu_tile_errors.argtypes = [vp, vp, vp, C.c_float, fp, vp]
+        L.vpt_gpu_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams), vp, vp, C.POINTER(C.c_uint32), fp,
+                                              C.POINTER(AdaptiveResult), vp]
     L.vpt_gpu_sync.argtypes = [vp]
     L.vpt_gpu_film_clear.argtypes = [vp]
     L.vpt_gpu_film_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]

@@ -65,9 +65,11 @@ struct FeedLaunch {
   uint32_t* tile_done;  // nullptr unless a staged feed
 };
 // A band launch (vpt_gpu_render_tiles): `waves` waves of the tiles [tile_lo, tile_lo + tiles), their samples in
-// groups of `group` waves (vpt_integrator.h band_slot).
+// groups of `group` waves (vpt_integrator.h band_slot).  A tile-list launch (vpt_gpu_render_tile_list): list = true,
+// the tiles are the context's uploaded list (list_dev, `tiles` of them; tile_lo is 0).
 struct BandLaunch {
   uint32_t tile_lo, tiles, waves, group;
+  bool list = false;
 };
 }  // namespace vpt
 
@@ -148,6 +150,18 @@ struct vpt_gpu_ctx {
   // ordered launches, one at a time (samples_done), so the next one may refill it on its stream.
   uint32_t* band_rank = nullptr;
   uint32_t band_rank_lo = 0, band_rank_hi = 0;
+  // Tile-list launches (vpt_gpu_render_tile_list): the list (list_dev, its first list_host.size() words) and the
+  // tile -> list index map (list_slot_dev, kNoListSlot for the other tiles), T words each, allocated with band_rank.
+  // list_host is the list they hold; list_ranked: band_rank holds this list's ranks.  Uploaded by the call itself
+  // once the previous ordered launch has read them (samples_done).
+  uint32_t* list_dev = nullptr;
+  uint32_t* list_slot_dev = nullptr;
+  std::vector<uint32_t> list_host, list_slot_host;
+  bool list_ranked = false;
+  // The second-moment plane (vpt_gpu_set_film_moments): the caller's float[H][W], written by the ordered film
+  // passes while attached.  tile_err: vpt_gpu_tile_errors' T results (device, allocated with band_rank).
+  float* m2 = nullptr;
+  float* tile_err = nullptr;
   // The drop-in's ordered frame (vpt_gpu_frame_open / _finish): its feed launches also store the samples of the
   // frame's tiles [frame_tile_lo, + frame_tiles) from job frame_jid_lo on into the sample buffer above, frame_waves
   // waves of those tiles (0: no frame open); the order pass writes frame_film (device, film_count floats), copied

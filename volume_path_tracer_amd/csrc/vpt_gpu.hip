@@ -188,6 +188,9 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->scene_full_dev);
   (void)hipFree(ctx->order);
   (void)hipFree(ctx->band_rank);
+  (void)hipFree(ctx->list_dev);
+  (void)hipFree(ctx->list_slot_dev);
+  (void)hipFree(ctx->tile_err);
   (void)hipFree(ctx->perm);
   (void)hipFree(ctx->samples);
   (void)hipFree(ctx->frame_film);
@@ -218,6 +221,11 @@ int rank_tiles(vpt_gpu_ctx* ctx) {
   // (band launches' filtered ranks: the context's one buffer, so that no launch allocates)
   if (!ctx->band_rank) VPT_HIP(hipMalloc((void**)&ctx->band_rank, T * sizeof(uint32_t)));
   ctx->band_rank_lo = ctx->band_rank_hi = 0;
+  // (tile-list launches' list and slot map, vpt_gpu_tile_errors' results: likewise)
+  if (!ctx->list_dev) VPT_HIP(hipMalloc((void**)&ctx->list_dev, T * sizeof(uint32_t)));
+  if (!ctx->list_slot_dev) VPT_HIP(hipMalloc((void**)&ctx->list_slot_dev, T * sizeof(uint32_t)));
+  if (!ctx->tile_err) VPT_HIP(hipMalloc((void**)&ctx->tile_err, T * sizeof(float)));
+  ctx->list_ranked = false;
   return VPT_OK;
 }
 
@@ -314,6 +322,14 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // can); each adds its own waves in order, so the film is the same.
   const uint64_t per_job = (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
   const bool ordered = ctx->film_order == VPT_FILM_ORDERED && !feed && !records && !events && !ctx->scene.pixel_mode;
+  // The moment plane (vpt_gpu_set_film_moments) is written by the ordered film passes only: a launch that would add
+  // with film atomics fails instead of leaving the plane behind the film.  (Feeds never write it.)
+  if (ctx->m2 && !feed && (!ordered || ctx->frame_waves))
+    return vpt::set_error(VPT_E_STATE, "render: a moment plane is attached and this launch would add with film atomics (" +
+                                           std::string(ctx->frame_waves ? "a frame is open"
+                                                       : records || events ? "a debug launch"
+                                                                           : "not an ordered launch of the reference RNG mode") +
+                                           "): detach it (vpt_gpu_set_film_moments NULL)");
   if (ordered && !band) {  // (vpt_gpu_render_tiles splits its launches itself: by waves)
     const uint64_t max_jobs = std::min<uint64_t>(ordered_cap(ctx, jid_count * per_job) / per_job, 0xffffffffULL);
     if (max_jobs == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one job's samples");
@@ -447,6 +463,9 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   } else if (ordered && !ctx->frame_waves && (rc = ensure_samples(ctx, jid_count * per_job, samples))) {
     return rc;
   }
+  if (ctx->m2 && !feed && !samples)
+    return vpt::set_error(VPT_E_STATE, "render: a moment plane is attached and the sample buffer would have to grow while "
+                                       "a feed of the context is open (the launch would add with film atomics)");
   env.samples = samples;
   if (samples) {
     ++ctx->ordered_launches;
@@ -459,14 +478,29 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
     // the launch's stream -- after the wait above, so after the previous band launch has read the buffer -- unless
     // the buffer still holds this band's.
     env.band_rank = ctx->order;
-    if (band->tile_lo != 0 || band->tiles != T) {
+    env.band_slot_map = nullptr;
+    if (band->list) {
+      // a tile list (uploaded by vpt_gpu_render_tile_list): its ranks are filtered by the slot map, once per list
+      if (!ctx->band_rank || !ctx->list_dev || !ctx->list_slot_dev)
+        return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tile_list: no tile-list buffers (their allocation failed)");
+      if (!ctx->list_ranked) {
+        hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, 0u, band->tiles,
+                           ctx->band_rank, ctx->list_slot_dev);
+        VPT_HIP(hipGetLastError());
+        ctx->band_rank_lo = ctx->band_rank_hi = 0;  // (no longer a band's)
+        ctx->list_ranked = true;
+      }
+      env.band_rank = ctx->band_rank;
+      env.band_slot_map = ctx->list_slot_dev;
+    } else if (band->tile_lo != 0 || band->tiles != T) {
       if (!ctx->band_rank) return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tiles: no tile-rank buffer (its allocation failed)");
       if (ctx->band_rank_lo != band->tile_lo || ctx->band_rank_hi != band->tile_lo + band->tiles) {
         hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, band->tile_lo,
-                           band->tile_lo + band->tiles, ctx->band_rank);
+                           band->tile_lo + band->tiles, ctx->band_rank, (const uint32_t*)nullptr);
         VPT_HIP(hipGetLastError());
         ctx->band_rank_lo = band->tile_lo;
         ctx->band_rank_hi = band->tile_lo + band->tiles;
+        ctx->list_ranked = false;
       }
       env.band_rank = ctx->band_rank;
     }
@@ -557,15 +591,18 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
   if (band) {  // the film's pixels of the band, in wave order (sample counts included)
     const uint32_t chunks = (ctx->scene.tile_area + 63u) / 64u;
-    hipLaunchKernelGGL(vpt::vpt_band_order_kernel, dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev, env.film,
-                       samples, band->tile_lo, band->waves, env.band_groups, band->group);
+    const uint32_t* const list = band->list ? ctx->list_dev : nullptr;
+    hipLaunchKernelGGL(ctx->m2 ? vpt::vpt_band_order_kernel<true> : vpt::vpt_band_order_kernel<false>,
+                       dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev, env.film, (const float*)samples,
+                       band->tile_lo, band->waves, env.band_groups, band->group, list, ctx->m2);
     VPT_HIP(hipGetLastError());
     VPT_HIP(hipEventRecord(ctx->samples_done, s));
     ctx->samples_used = true;
   } else if (samples) {  // the film, pixel by pixel in wave order (sample counts included)
     const uint64_t threads = ctx->scene.T * (uint64_t)ctx->scene.tile_area;
-    hipLaunchKernelGGL(vpt::vpt_film_order_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
-                       ctx->scene_dev, env.film, samples, jid_begin, jid_count);
+    hipLaunchKernelGGL(ctx->m2 ? vpt::vpt_film_order_kernel<true> : vpt::vpt_film_order_kernel<false>,
+                       dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ctx->scene_dev, env.film,
+                       (const float*)samples, jid_begin, jid_count, ctx->m2);
     VPT_HIP(hipGetLastError());
     VPT_HIP(hipEventRecord(ctx->samples_done, s));
     ctx->samples_used = true;
@@ -789,6 +826,28 @@ int check_device(int device, const char* what) {
   if (device < 0 || device >= ndev) return vpt::set_error(VPT_E_INVALID, std::string(what) + ": bad device index");
   return VPT_OK;
 }
+
+// The launches of vpt_gpu_render_tiles and vpt_gpu_render_tile_list (list: the context's uploaded list, B tiles;
+// tile_lo 0), arguments checked: `wave_count` > 0 waves from wave_begin of the band's B tiles.
+// The cap (vpt_gpu_set_film_order's max_bytes, else what the device has free): consecutive blocks of waves, each
+// with its own film pass, in wave order -- the same film.  Whole groups of 64 waves where the cap allows; below
+// that a block's group is as wide as the block, so its buffer is no larger than its waves' samples.
+int render_band_waves(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t B, bool list, uint64_t wave_begin, uint64_t wave_count,
+                      float* film_device, void* hip_stream) {
+  const uint64_t T = ctx->scene.T, G = vpt::kBandGroup;
+  const uint64_t per_wave = (uint64_t)B * (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
+  const uint64_t max_waves = ordered_cap(ctx, (wave_count + G - 1) / G * G * per_wave) / per_wave;
+  if (max_waves == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one wave of the band's samples");
+  const uint64_t chunk = max_waves >= G ? max_waves / G * G : max_waves;
+  for (uint64_t b = 0; b < wave_count; b += chunk) {
+    const uint64_t n = std::min(chunk, wave_count - b);
+    const vpt::BandLaunch band{tile_lo, B, (uint32_t)n, (uint32_t)(max_waves >= G ? G : n), list};
+    if (int rc = render(ctx, (wave_begin + b) * T, (uint64_t)B * n, film_device, nullptr, hip_stream, nullptr, 0, nullptr,
+                        nullptr, &band))
+      return rc;
+  }
+  return VPT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -898,19 +957,136 @@ int vpt_gpu_render_tiles(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t tile_hi, u
   if (ctx->frame_waves)
     return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tiles: a frame is open (vpt_gpu_frame_open owns the sample buffer)");
   if (wave_count == 0) return VPT_OK;
-  // The cap (vpt_gpu_set_film_order's max_bytes, else what the device has free): consecutive blocks of waves, each
-  // with its own film pass, in wave order -- the same film.  Whole groups of 64 waves where the cap allows; below
-  // that a block's group is as wide as the block, so its buffer is no larger than its waves' samples.
-  const uint64_t per_wave = B * (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
-  const uint64_t max_waves = ordered_cap(ctx, (wave_count + G - 1) / G * G * per_wave) / per_wave;
-  if (max_waves == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one wave of the band's samples");
-  const uint64_t chunk = max_waves >= G ? max_waves / G * G : max_waves;
-  for (uint64_t b = 0; b < wave_count; b += chunk) {
-    const uint64_t n = std::min(chunk, wave_count - b);
-    const vpt::BandLaunch band{tile_lo, (uint32_t)B, (uint32_t)n, (uint32_t)(max_waves >= G ? G : n)};
-    if ((rc = render(ctx, (wave_begin + b) * T, B * n, film_device, nullptr, hip_stream, nullptr, 0, nullptr, nullptr, &band)))
-      return rc;
+  return render_band_waves(ctx, tile_lo, (uint32_t)B, false, wave_begin, wave_count, film_device, hip_stream);
+}
+
+int vpt_gpu_render_tile_list(vpt_gpu_ctx* ctx, const uint32_t* tiles, uint32_t n, uint64_t wave_begin, uint64_t wave_count,
+                             float* film_device, void* hip_stream) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tile_list: null context");
+  if (n && !tiles) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tile_list: null tile list");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  const uint64_t T = ctx->scene.T;
+  for (uint32_t i = 0; i < n; ++i)
+    if (tiles[i] >= T || (i && tiles[i] <= tiles[i - 1]))
+      return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tile_list: the list must be strictly ascending tile indices < T");
+  if (ctx->scene.pixel_mode)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tile_list: list launches run the reference RNG mode");
+  const uint64_t G = vpt::kBandGroup;  // (the same 32-bit limits as vpt_gpu_render_tiles)
+  if (wave_count >= (1ULL << 32) || (wave_count + G - 1) / G * G * T >= (1ULL << 32) || wave_begin > (UINT64_MAX / T) - wave_count)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_tile_list: 2^32 or more sample slots (render fewer waves per call)");
+  if (ctx->film_order != VPT_FILM_ORDERED)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tile_list: list launches need the ordered film "
+                                       "(vpt_gpu_set_film_order: VPT_FILM_ORDERED)");
+  if (ctx->frame_waves)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tile_list: a frame is open (vpt_gpu_frame_open owns the sample buffer)");
+  if (ctx->open_feeds.load() > 0)  // (the upload below would wait for the feed's launch, which holds the device)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tile_list: a feed of this context is open");
+  if (wave_count == 0 || n == 0) return VPT_OK;
+  if ((rc = ensure_order(ctx))) return rc;  // (allocates the list's buffers with the tile ranks)
+  if (ctx->list_host.size() != n || !std::equal(tiles, tiles + n, ctx->list_host.begin())) {
+    // The previous ordered launch may still read the list and the map (its film pass, its kernels' job starts).
+    if (ctx->samples_used) VPT_HIP(hipEventSynchronize(ctx->samples_done));
+    ctx->list_host.clear();  // (nothing valid on the device until both copies are done)
+    ctx->list_ranked = false;
+    ctx->list_slot_host.assign(T, vpt::kNoListSlot);
+    for (uint32_t i = 0; i < n; ++i) ctx->list_slot_host[tiles[i]] = i;
+    VPT_HIP(hipMemcpy(ctx->list_dev, tiles, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    VPT_HIP(hipMemcpy(ctx->list_slot_dev, ctx->list_slot_host.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->list_host.assign(tiles, tiles + n);
   }
+  return render_band_waves(ctx, 0, n, true, wave_begin, wave_count, film_device, hip_stream);
+}
+
+int vpt_gpu_set_film_moments(vpt_gpu_ctx* ctx, float* m2_device) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_film_moments: null context");
+  if (m2_device && ctx->film_order != VPT_FILM_ORDERED)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_film_moments: the plane is written by the ordered film passes "
+                                       "(vpt_gpu_set_film_order: VPT_FILM_ORDERED)");
+  if (m2_device && ctx->frame_waves)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_film_moments: a frame is open (its launches add with film atomics)");
+  ctx->m2 = m2_device;  // read by the next render's host code only: no wait
+  return VPT_OK;
+}
+
+int vpt_gpu_tile_errors(vpt_gpu_ctx* ctx, const float* film_device, const float* m2_device, float abs_floor,
+                        float* err_T_host, void* hip_stream) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_tile_errors: null context");
+  if (!m2_device || !err_T_host || !(abs_floor > 0.0f))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_tile_errors: needs a moment plane, an output array and abs_floor > 0");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0)  // (the call waits for its kernel, which would wait for the feed's launch)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_tile_errors: a feed of this context is open");
+  uint32_t P = 1;
+  while (P < ctx->scene.tile_area) P <<= 1;
+  if (P > vpt::kTileErrorMaxP)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_tile_errors: tiles of more than " + std::to_string(vpt::kTileErrorMaxP) +
+                                             " pixels are not supported (the tree is reduced in LDS)");
+  if ((rc = ensure_order(ctx))) return rc;  // (allocates the result buffer with the tile ranks)
+  hipStream_t s = (hipStream_t)hip_stream;
+  const uint32_t T = (uint32_t)ctx->scene.T;
+  hipLaunchKernelGGL(vpt::vpt_tile_error_kernel, dim3(T), dim3(vpt::kTileErrorThreads), 2 * (size_t)P * sizeof(float), s,
+                     ctx->scene_dev, film_device ? film_device : (const float*)ctx->film, m2_device, abs_floor, P,
+                     ctx->tile_err);
+  VPT_HIP(hipGetLastError());
+  VPT_HIP(hipMemcpyAsync(err_T_host, ctx->tile_err, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, s));
+  VPT_HIP(hipStreamSynchronize(s));
+  return VPT_OK;
+}
+
+int vpt_gpu_render_adaptive(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p, float* film_device, float* m2_device,
+                            uint32_t* waves_T_host, float* err_T_host, vpt_adaptive_result* out, void* hip_stream) {
+  if (!ctx || !p || !m2_device || !waves_T_host || !err_T_host)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive: null argument");
+  if (p->min_waves < 2 || p->step_waves == 0 || p->max_waves < p->min_waves || !(p->target_error >= 0.0f) ||
+      !(p->abs_floor > 0.0f))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive: needs min_waves >= 2, step_waves >= 1, max_waves >= "
+                                         "min_waves, target_error >= 0 and abs_floor > 0");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  const uint32_t T = (uint32_t)ctx->scene.T;
+  float* const film = film_device ? film_device : ctx->film;
+  float* const prev = ctx->m2;
+  if ((rc = vpt_gpu_set_film_moments(ctx, m2_device))) return rc;
+  struct Restore {  // the previous attachment, on every return
+    vpt_gpu_ctx* c;
+    float* m2;
+    ~Restore() { c->m2 = m2; }
+  } restore{ctx, prev};
+  vpt_adaptive_result res{};
+  res.jobs_uniform = (uint64_t)p->max_waves * T;
+  // Round 0: the first min_waves waves of every tile.
+  if ((rc = vpt_gpu_render_tiles(ctx, 0, T, 0, p->min_waves, film, hip_stream))) return rc;
+  std::fill(waves_T_host, waves_T_host + T, p->min_waves);
+  res.rounds = 1;
+  res.jobs_rendered = (uint64_t)p->min_waves * T;
+  // Later rounds: the tiles still above the target and below the cap, all at the same wave count (a tile that
+  // leaves the list never returns), get the next step_waves waves in one list launch.
+  std::vector<uint32_t> list(T), next;
+  for (uint32_t t = 0; t < T; ++t) list[t] = t;
+  uint32_t done = p->min_waves;
+  for (;;) {
+    if ((rc = vpt_gpu_tile_errors(ctx, film, m2_device, p->abs_floor, err_T_host, hip_stream))) return rc;
+    if (done >= p->max_waves) break;
+    next.clear();
+    const bool never = p->target_error == 0.0f;  // (no tile stops: black tiles, whose estimate is 0, neither)
+    for (uint32_t t : list)
+      if (never || err_T_host[t] > p->target_error) next.push_back(t);
+    list.swap(next);
+    if (list.empty()) break;
+    const uint32_t step = std::min(p->step_waves, p->max_waves - done);
+    if ((rc = vpt_gpu_render_tile_list(ctx, list.data(), (uint32_t)list.size(), done, step, film, hip_stream))) return rc;
+    for (uint32_t t : list) waves_T_host[t] += step;
+    done += step;
+    ++res.rounds;
+    res.jobs_rendered += (uint64_t)step * list.size();
+  }
+  for (uint32_t t = 0; t < T; ++t) {
+    if (waves_T_host[t] >= p->max_waves) ++res.tiles_at_max;
+    res.max_error = std::max(res.max_error, err_T_host[t]);
+  }
+  if (out) *out = res;
   return VPT_OK;
 }
 

@@ -96,6 +96,9 @@ struct KernelArgs {
   uint32_t band_tile_lo;
   uint32_t band_groups;
   uint32_t band_group;
+  // A tile-list launch (vpt_gpu_render_tile_list): a band launch whose tiles are a list; tile t's index in the list
+  // (the tb of band_slot) is band_slot_map[t].  nullptr: a contiguous band, tb = t - band_tile_lo.
+  const uint32_t* band_slot_map;
 };
 typedef const __attribute__((address_space(4))) KernelArgs* ArgsPtr;
 // This workgroup's event counters and (VPT_PROFILE builds) section cycles; the temperature kernel's LDS copy of
@@ -339,7 +342,9 @@ struct KernelEnvT {
   __device__ __forceinline__ void job_start(const DevScene& S, LaneCold& lc, uint64_t jid) {
     if constexpr (Band) {
       (void)jid;
-      const uint32_t T = args()->band_T, w = lc.item_lo / T, tb = lc.item_lo - w * T - args()->band_tile_lo;
+      const uint32_t T = args()->band_T, w = lc.item_lo / T, tile = lc.item_lo - w * T;
+      const uint32_t* const map = args()->band_slot_map;  // (a tile list's; uniform, once per job)
+      const uint32_t tb = map ? map[tile] : tile - args()->band_tile_lo;
       const uint64_t a = (uint64_t)(args()->samples + band_slot(tb, w, 0, args()->band_groups, S.tile_area, args()->band_group));
       lc.item_lo = (uint32_t)a;
       lc.item_hi = (uint32_t)(a >> 32);
@@ -693,8 +698,12 @@ __global__ void vpt_tile_count_kernel(const DevScene* scene, float* film, const 
 // w += 1, xyz += imaging_ratio * L).  So the film equals the reference's bit for bit, whatever order the
 // launch ran its jobs in.  One thread per (tile, local pixel), so a wavefront reads one job's samples as one
 // contiguous run (12 B per pixel) per wave; the film's float4 is read and written once.
+// Moments (vpt_gpu_set_film_moments): the pixel's second moment of Y in m2[py * W + px], m2 += (r * L.y)^2 per sample
+// after the four adds, in the same wave order; read and written once, as the float4 is.  The instantiation without
+// it is the pass as it was (m2 unused).
+template <bool Moments>
 __global__ void vpt_film_order_kernel(const DevScene* scene, float* film, const float* samples, uint64_t jid_begin,
-                                      uint64_t jid_count) {
+                                      uint64_t jid_count, float* m2) {
   const DevScene& S = *scene;
   const uint32_t area = S.tile_area;
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -715,12 +724,28 @@ __global__ void vpt_film_order_kernel(const DevScene* scene, float* film, const 
   const float* s = samples + ((t + k0 * T - jid_begin) * area + q) * 3;
   const uint64_t step = T * area * 3;
   const uint64_t n = (end - 1 - t) / T - k0 + 1;
+  if constexpr (Moments) {
+    float* const mp = m2 + ((uint64_t)py * (uint64_t)S.W + (uint64_t)px);
+    float m = *mp;
 #pragma unroll 8
-  for (uint64_t k = 0; k < n; ++k, s += step) {
-    a.w = a.w + 1.0f;
-    a.x = a.x + r * s[0];
-    a.y = a.y + r * s[1];
-    a.z = a.z + r * s[2];
+    for (uint64_t k = 0; k < n; ++k, s += step) {
+      const float y = r * s[1];
+      a.w = a.w + 1.0f;
+      a.x = a.x + r * s[0];
+      a.y = a.y + y;
+      a.z = a.z + r * s[2];
+      m = m + y * y;
+    }
+    *mp = m;
+  } else {
+    (void)m2;
+#pragma unroll 8
+    for (uint64_t k = 0; k < n; ++k, s += step) {
+      a.w = a.w + 1.0f;
+      a.x = a.x + r * s[0];
+      a.y = a.y + r * s[1];
+      a.z = a.z + r * s[2];
+    }
   }
   *f = a;
 }
@@ -765,16 +790,19 @@ __global__ void vpt_frame_order_kernel(const DevScene* scene, float* film, const
 
 // A band launch's tile ranks (vpt_gpu_render_tiles): `order` (the T tiles by descending cost) filtered to the tiles
 // [lo, hi), in the same sequence, into out[0 .. hi - lo).  One block: every 256 entries, a wavefront ranks its
-// band tiles with a ballot and the block's four counts give each wavefront its base.
+// band tiles with a ballot and the block's four counts give each wavefront its base.  A tile list's
+// (vpt_gpu_render_tile_list): slot_map != nullptr, the members are the tiles t with slot_map[t] != kNoListSlot,
+// hi - lo of them (lo = 0, hi = the list's length).
+constexpr uint32_t kNoListSlot = 0xffffffffu;
 __global__ __launch_bounds__(256) void vpt_band_rank_kernel(const uint32_t* order, uint32_t T, uint32_t lo, uint32_t hi,
-                                                            uint32_t* out) {
+                                                            uint32_t* out, const uint32_t* slot_map) {
   __shared__ uint32_t cnt[4];
   const uint32_t wave = threadIdx.x >> 6;
   uint32_t base = 0;
   for (uint32_t i0 = 0; i0 < T; i0 += 256) {  // (uniform)
     const uint32_t i = i0 + threadIdx.x;
     const uint32_t t = i < T ? order[i] : 0u;
-    const bool in = i < T && t >= lo && t < hi;
+    const bool in = i < T && t < T && (slot_map ? slot_map[t] != kNoListSlot : (t >= lo && t < hi));
     const uint64_t m = __builtin_amdgcn_ballot_w64(in);
     const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
     if ((threadIdx.x & 63u) == 0) cnt[wave] = (uint32_t)__popcll(m);
@@ -808,15 +836,20 @@ __global__ __launch_bounds__(256) void vpt_band_rank_kernel(const uint32_t* orde
 // with 4-B ones.  The last group's padding and ragged tiles' missing pixels are staged (the buffer holds them)
 // but never added.
 constexpr uint32_t kBandStageWaves = 16;
+//
+// A tile list's pass (vpt_gpu_render_tile_list): list != nullptr, and the block's tile is list[tb] instead of
+// tile_lo + tb.  Moments: the second-moment plane, as in vpt_film_order_kernel.
 constexpr uint32_t kBandStageStride = kBandStageWaves * 3 + 1;
+template <bool Moments>
 __global__ __launch_bounds__(64) void vpt_band_order_kernel(const DevScene* scene, float* film, const float* samples,
-                                                            uint32_t tile_lo, uint32_t waves, uint32_t groups, uint32_t G) {
+                                                            uint32_t tile_lo, uint32_t waves, uint32_t groups, uint32_t G,
+                                                            const uint32_t* list, float* m2) {
   __shared__ float stage[64 * kBandStageStride];
   const DevScene& S = *scene;
   const uint32_t area = S.tile_area, chunks = (area + 63u) / 64u;
   const uint32_t tb = blockIdx.x / chunks, q0 = (blockIdx.x - tb * chunks) * 64u;
   const uint32_t np = min(64u, area - q0);  // the block's pixels q0 .. q0 + np of the tile
-  const uint32_t t = tile_lo + tb, q = q0 + threadIdx.x;
+  const uint32_t t = list ? list[tb] : tile_lo + tb, q = q0 + threadIdx.x;
   const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
   const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
   bool mine = threadIdx.x < np && (int32_t)q < rw * rh;
@@ -825,6 +858,10 @@ __global__ __launch_bounds__(64) void vpt_band_order_kernel(const DevScene* scen
   float4* const f = reinterpret_cast<float4*>(film) + ((uint64_t)py * (uint64_t)S.W + (uint64_t)px);
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   if (mine) a = *f;
+  float* const mp = Moments ? m2 + ((uint64_t)py * (uint64_t)S.W + (uint64_t)px) : nullptr;
+  float m = 0.0f;
+  if constexpr (Moments)
+    if (mine) m = *mp;
   const float r = S.imaging_ratio;
   const bool vec = (G & 3u) == 0;
   const float* const row = stage + threadIdx.x * kBandStageStride;
@@ -854,17 +891,89 @@ __global__ __launch_bounds__(64) void vpt_band_order_kernel(const DevScene* scen
         }
       }
       __syncthreads();
-      if (mine)
-        for (uint32_t k = 0; k < cw; ++k) {  // (in wave order, never reduced across waves)
-          a.w = a.w + 1.0f;
-          a.x = a.x + r * row[3 * k];
-          a.y = a.y + r * row[3 * k + 1];
-          a.z = a.z + r * row[3 * k + 2];
+      if (mine) {
+        if constexpr (Moments) {
+          for (uint32_t k = 0; k < cw; ++k) {  // (in wave order, never reduced across waves)
+            const float y = r * row[3 * k + 1];
+            a.w = a.w + 1.0f;
+            a.x = a.x + r * row[3 * k];
+            a.y = a.y + y;
+            a.z = a.z + r * row[3 * k + 2];
+            m = m + y * y;
+          }
+        } else {
+          for (uint32_t k = 0; k < cw; ++k) {  // (in wave order, never reduced across waves)
+            a.w = a.w + 1.0f;
+            a.x = a.x + r * row[3 * k];
+            a.y = a.y + r * row[3 * k + 1];
+            a.z = a.z + r * row[3 * k + 2];
+          }
         }
+      }
       __syncthreads();  // the stage is rewritten
     }
   }
-  if (mine) *f = a;
+  if (mine) {
+    *f = a;
+    if constexpr (Moments) *mp = m;
+  }
+}
+
+// Per-tile error estimates (vpt_gpu_tile_errors): one block per tile.  Pixel q of the tile (local index) is counted
+// when it lies in the image, is the single pixel in that mode, and holds n = film.w >= 2 samples; a counted pixel
+// contributes se = sqrt(max(m2 / n - mean^2, 0) / (n - 1)) and mean = film.y / n, any other +0.0.  Both arrays,
+// padded with +0.0 to P (the power of two >= the tile area; 2 * P floats of dynamic LDS), are reduced by the fixed
+// tree a[i] += a[i + h], h = P / 2 .. 1 -- levels wider than the block as a strided loop -- and
+// err = sum(se) / (sum(mean) + abs_floor * count), 0 for a tile without counted pixels.  All fp32, in this order:
+// the contract of include/vpt_gpu.h, restated in numpy by the tests.
+constexpr uint32_t kTileErrorThreads = 256;
+constexpr uint32_t kTileErrorMaxP = 8192;  // 64 KiB of LDS
+__global__ __launch_bounds__(kTileErrorThreads) void vpt_tile_error_kernel(const DevScene* scene, const float* film,
+                                                                            const float* m2, float abs_floor, uint32_t P,
+                                                                            float* err) {
+  extern __shared__ float tile_err_lds[];
+  __shared__ uint32_t counted;
+  float* const se = tile_err_lds;
+  float* const mean = tile_err_lds + P;
+  const DevScene& S = *scene;
+  const uint32_t t = blockIdx.x;
+  const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
+  const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
+  if (threadIdx.x == 0) counted = 0;
+  __syncthreads();
+  uint32_t cnt = 0;
+  for (uint32_t q = threadIdx.x; q < P; q += kTileErrorThreads) {
+    float e = 0.0f, mu = 0.0f;
+    if ((int32_t)q < rw * rh) {
+      const int32_t yl = (int32_t)q / rw, px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
+      const uint64_t p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
+      const float4 f = reinterpret_cast<const float4*>(film)[p];
+      const float n = f.w;
+      if (!(S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) && n >= 2.0f) {
+        mu = f.y / n;
+        const float ex2 = m2[p] / n;
+        float v = ex2 - mu * mu;
+        if (!(v > 0.0f)) v = 0.0f;
+        e = sqrtf(v / (n - 1.0f));
+        ++cnt;
+      }
+    }
+    se[q] = e;
+    mean[q] = mu;
+  }
+  if (cnt) atomicAdd(&counted, cnt);
+  __syncthreads();
+  for (uint32_t h = P >> 1; h >= 1; h >>= 1) {  // (uniform bounds: the barriers are too)
+    for (uint32_t i = threadIdx.x; i < h; i += kTileErrorThreads) {
+      se[i] = se[i] + se[i + h];
+      mean[i] = mean[i] + mean[i + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const uint32_t c = counted;
+    err[t] = c ? se[0] / (mean[0] + abs_floor * (float)c) : 0.0f;
+  }
 }
 
 // The drop-in's seed recovery (include/vpt_run.hpp rng_seed): the reference's RandomNumberGenerator keeps its u32

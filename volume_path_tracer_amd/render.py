@@ -200,6 +200,49 @@ class Integrator:
                                                    int(num_waves), C.c_void_p(film.data_ptr()),
                                                    C.c_void_p(self.stream_handle(stream))), "vpt_gpu_render_tiles")
 
+    def _check_plane(self, m2) -> None:
+        assert m2.is_cuda and m2.dtype == self.torch.float32 and m2.is_contiguous()
+        assert m2.numel() == self.cfg.height * self.cfg.width
+
+    def set_film_moments(self, m2) -> None:
+        """Attach a second-moment plane (a device float32 [H][W] tensor; None detaches): while attached, the ordered
+        film passes also add (imaging_ratio * L.y)^2 of every sample into it, in wave order
+        (vpt_gpu_set_film_moments).  The tensor is kept alive while it is attached."""
+        if m2 is not None:
+            self._check_plane(m2)
+        capi.check(capi.lib().vpt_gpu_set_film_moments(self.h, C.c_void_p(m2.data_ptr()) if m2 is not None else None),
+                   "vpt_gpu_set_film_moments")
+        self._m2 = m2
+
+    def render_tile_list(self, tiles, first_wave: int, num_waves: int, film=None, stream=None):
+        """render_tiles for an arbitrary list of tiles (strictly ascending indices < T) with one list launch
+        (vpt_gpu_render_tile_list); waves are 1-based, as render_tiles."""
+        film = self.film if film is None else film
+        assert film.is_cuda and film.dtype == self.torch.float32 and film.is_contiguous()
+        assert film.numel() == self.cfg.height * self.cfg.width * 4
+        if first_wave < 1 or num_waves < 0:
+            raise ValueError("render_tile_list: waves are 1-based, num_waves >= 0")
+        t = np.asarray(tiles, dtype=np.int64).reshape(-1)
+        if t.size and (t.min() < 0 or t.max() > 0xFFFFFFFF):
+            raise ValueError("render_tile_list: tile indices are 32-bit")
+        t = np.ascontiguousarray(t, np.uint32)
+        capi.check(capi.lib().vpt_gpu_render_tile_list(self.h, t.ctypes.data_as(C.POINTER(C.c_uint32)), int(t.size),
+                                                       int(first_wave) - 1, int(num_waves), C.c_void_p(film.data_ptr()),
+                                                       C.c_void_p(self.stream_handle(stream))), "vpt_gpu_render_tile_list")
+
+    def tile_errors(self, m2, film=None, abs_floor: float = 1e-3, stream=None) -> np.ndarray:
+        """Per-tile error estimates float32[T] of `film` (default: own) and its moment plane `m2`
+        (vpt_gpu_tile_errors: the tile's mean standard error of Y over its mean Y); synchronous."""
+        film = self.film if film is None else film
+        assert film.is_cuda and film.dtype == self.torch.float32 and film.is_contiguous()
+        assert film.numel() == self.cfg.height * self.cfg.width * 4
+        self._check_plane(m2)
+        err = np.zeros(self.cfg.jobs_per_wave(), np.float32)
+        capi.check(capi.lib().vpt_gpu_tile_errors(self.h, C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                                  float(abs_floor), err.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  C.c_void_p(self.stream_handle(stream))), "vpt_gpu_tile_errors")
+        return err
+
     def trace_jobs(self, jid_begin: int, jid_count: int, capacity: int = 1 << 20, film=None, stream=None):
         """Render jobs and return their Logger events (worker.cpp:16-48) as a numpy array of
         capi.EVENT_DTYPE sorted by (jid, seq).  Raises if more than `capacity` events occur."""
@@ -454,6 +497,29 @@ def run(cfg: capi.Configuration, integrator: Integrator, tp: TileProvider, film:
     finally:
         feed.destroy()
     return out
+
+
+def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, step_waves: int = 64,
+                    max_waves: Optional[int] = None, abs_floor: float = 1e-3):
+    """Render a frame from zero until every tile's error estimate (Integrator.tile_errors) is at most
+    `target_error` or it has `max_waves` waves (None: cfg.num_waves): `min_waves` waves of every tile, then
+    `step_waves` more per round of the tiles still above the target (vpt_gpu_render_adaptive).  Each tile's film
+    is the uniform frame's after its own wave count, bit for bit.
+    -> (film float32[H][W][4], waves uint32[T], err float32[T], info dict)."""
+    torch = it.torch
+    T = it.cfg.jobs_per_wave()
+    film = torch.zeros_like(it.film)
+    m2 = torch.zeros((it.cfg.height, it.cfg.width), dtype=torch.float32, device=it.dev)
+    torch.cuda.synchronize(it.dev)
+    p = capi.AdaptiveParams(float(target_error), float(abs_floor), int(min_waves), int(step_waves),
+                            int(it.cfg.num_waves if max_waves is None else max_waves))
+    res = capi.AdaptiveResult()
+    waves, err = np.zeros(T, np.uint32), np.zeros(T, np.float32)
+    capi.check(capi.lib().vpt_gpu_render_adaptive(it.h, C.byref(p), C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                                  waves.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res),
+                                                  C.c_void_p(it.stream_handle(None))), "vpt_gpu_render_adaptive")
+    return film.cpu().numpy(), waves, err, res.as_dict()
 
 
 def film_to_xyz(film: np.ndarray) -> np.ndarray:
