@@ -368,6 +368,33 @@ typedef struct vpt_adaptive_result {
 int vpt_gpu_render_adaptive(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p, float* film_device, float* m2_device,
                             uint32_t* waves_T_host, float* err_T_host, vpt_adaptive_result* out, void* hip_stream);
 
+/* The adaptive driver in one launch.  The same contract, arguments, outputs and parameter errors as
+ * vpt_gpu_render_adaptive, and the same bytes: film, plane, waves_T_host, err_T_host and *out equal the rounds
+ * driver's bit for bit (rounds = 1 + the later boundaries the longest-running tile crossed).  The stopping rule is per
+ * tile, so no round needs the others: a wavefront of the throughput kernel owns a tile.  It claims tiles by
+ * descending cost (vpt_gpu_tile_costs' ranks) from a counter; renders the tile's waves in groups of up to 64, one job
+ * per lane, up to the next boundary (min_waves, then + step_waves each time, cut at max_waves); adds each group's
+ * samples into the tile's film and plane pixels itself, in wave order, with the ordered film passes' sequence; at a
+ * boundary evaluates the tile's estimate with vpt_gpu_tile_errors' arithmetic and tree and goes on iff
+ * (target_error == 0 || err > target_error) and the tile is below max_waves; else stores the tile's waves and error
+ * and claims again.  No host read-back, no drain between rounds, and no lane ever waits for another wavefront.
+ *   Synchronous; the caller zeroes film_device (NULL = the context's film) and m2_device.  The plane is passed to
+ *   the launch directly: the context's attachment (vpt_gpu_set_film_moments) is neither used, changed nor written.
+ *   One ordered launch in vpt_gpu_film_order_info, on the throughput kernel's full resident grid (wavefronts beyond
+ *   the T tiles end at their first claim) with the full-launch gates.
+ *   Memory: the context's sample buffer is neither used nor resized and max_bytes does not apply.  The context keeps
+ *   wavefronts x tile_w*tile_h x 64 x 12 bytes of scratch (8 x 8 tiles on a full grid: about 350 MB) and T words of
+ *   wave counts, allocated by the first call and freed by vpt_gpu_destroy.  Two calls on one context must not
+ *   overlap (they share that scratch).
+ *   Limit: tiles of at most 256 pixels (tile_w*tile_h; the error tree is held in registers, four values per lane) --
+ *   VPT_E_INVALID beyond; vpt_gpu_render_adaptive renders larger tiles.
+ * VPT_E_INVALID also for the pixel RNG mode.  VPT_E_STATE with VPT_FILM_ATOMIC, while a frame is open, and while a
+ * feed of the context is launched and not closed (the call allocates and waits for its launch).  Not covered, as for
+ * the rounds driver: the drop-in vpt_gpu::run, the multi-GPU modes, feeds, the pixel RNG mode. */
+int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p, float* film_device, float* m2_device,
+                                  uint32_t* waves_T_host, float* err_T_host, vpt_adaptive_result* out,
+                                  void* hip_stream);
+
 /* The drop-in's ordered frame (vpt_run.hpp: vpt_gpu::run's film, bit-identical to the reference's).  A feed's jobs
  * arrive in the provider's order and its film is progressive, so its launch adds samples with fp32 atomics; with a
  * frame open, the context's feed launches also store the samples of the jobs of tiles [tile_lo, tile_hi) in waves

@@ -4,7 +4,9 @@
 
 The uniform frame (the config's size and spp) is timed with and without the moment plane attached; its own per-tile
 errors (vpt_gpu_tile_errors) give the targets: their 50th, 75th and 90th percentile.  vpt_gpu_render_adaptive then
-runs at each target and each step width, `reps` times, alternating with nothing else in the process.  Every timing
+runs at each target and each step width, `reps` times after a warm-up, interleaved rep by rep with the one-launch
+driver (vpt_gpu_render_adaptive_fused, whose waves and errors must equal the rounds driver's) and the uniform frame,
+so the three legs share the session's clocks.  Every timing
 is synchronised wall time around the whole driver call (it is synchronous: its rounds read the errors back), film
 and plane zeroed outside it; the uniform frame is timed the same way around render_jobs + synchronize.  Best and
 worst of the repetitions are reported (measuring-on-mi355x: warm up, repeat, report the spread).  Prints one JSON
@@ -89,6 +91,8 @@ def main():
            "runs": []}
     waves, err = np.zeros(T, np.uint32), np.zeros(T, np.float32)
     res = capi.AdaptiveResult()
+    waves_f, err_f, res_f = np.zeros(T, np.uint32), np.zeros(T, np.float32), capi.AdaptiveResult()
+    has_fused = hasattr(L, "vpt_gpu_render_adaptive_fused")  # (older builds in A/B runs lack it)
     # round 0 alone (target inf: every tile stops after min_waves) -- the driver's fixed part
     p_inf = capi.AdaptiveParams(float("inf"), args.abs_floor, args.min, 64, cap)
 
@@ -99,21 +103,44 @@ def main():
                    "vpt_gpu_render_adaptive")
 
     out["round0_only"] = stats([wall(round0) for _ in range(args.reps + 1)][1:])
+    if has_fused:  # the fused driver's: one group of min_waves lanes per tile, every wavefront draining on its slowest lane
+
+        def round0_fused():
+            capi.check(L.vpt_gpu_render_adaptive_fused(it.h, C.byref(p_inf), C.c_void_p(film.data_ptr()),
+                                                       C.c_void_p(m2.data_ptr()), waves.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                       err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res), s),
+                       "vpt_gpu_render_adaptive_fused")
+
+        out["round0_only_fused"] = stats([wall(round0_fused) for _ in range(args.reps + 1)][1:])
     launches0 = it.film_order_info()["ordered_launches"]
     for pct in [float(x) for x in args.percentiles.split(",")]:
         target = float(np.percentile(err_u, pct))
         for step in [int(x) for x in args.steps.split(",")]:
             p = capi.AdaptiveParams(target, args.abs_floor, args.min, step, cap)
 
-            def run():
-                capi.check(L.vpt_gpu_render_adaptive(it.h, C.byref(p), C.c_void_p(film.data_ptr()),
-                                                     C.c_void_p(m2.data_ptr()), waves.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                     err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res), s),
-                           "vpt_gpu_render_adaptive")
+            def run(fused=False):
+                name = "vpt_gpu_render_adaptive_fused" if fused else "vpt_gpu_render_adaptive"
+                capi.check(getattr(L, name)(it.h, C.byref(p), C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                            (waves_f if fused else waves).ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            (err_f if fused else err).ctypes.data_as(C.POINTER(C.c_float)),
+                                            C.byref(res_f if fused else res), s), name)
 
-            ms = [wall(run) for _ in range(args.reps + 1)][1:]  # (the first: warm-up, dropped)
+            # one warm-up of each leg (dropped), then the legs interleaved rep by rep: fused, rounds, uniform
+            wall(run)
             n_launch = it.film_order_info()["ordered_launches"] - launches0
-            launches0 += n_launch
+            ms, ms_f, ms_u = [], [], []
+            if has_fused:
+                wall(lambda: run(True))
+            for _ in range(args.reps):
+                if has_fused:
+                    ms_f.append(wall(lambda: run(True)))
+                    film_f = film.clone()
+                ms.append(wall(run))
+                if has_fused:  # the same frame, or the comparison means nothing
+                    assert waves_f.tobytes() == waves.tobytes() and err_f.tobytes() == err.tobytes()
+                    assert torch.equal(film_f, film) and res_f.rounds == res.rounds
+                ms_u.append(wall(lambda: it.render_jobs(0, cap * T, film=film)))
+            launches0 = it.film_order_info()["ordered_launches"]
             vals, counts = np.unique(waves, return_counts=True)
             # Where the time goes: the tiles that reached the cap, all their waves as ONE list launch (what their
             # work costs when it is not cut into rounds), and the launch of one later round alone (the first
@@ -128,7 +155,10 @@ def main():
                 launches0 = it.film_order_info()["ordered_launches"]
             out["runs"].append({"percentile": pct, "target": target, "step_waves": step, **stats(ms), **extra,
                                 "jobs_ratio": round(res.jobs_rendered / res.jobs_uniform, 4), "rounds": int(res.rounds),
-                                "launches_per_frame": n_launch // (args.reps + 1),
+                                "launches_per_frame": n_launch,
+                                "fused": stats(ms_f) if has_fused else None, "uniform_interleaved": stats(ms_u),
+                                "fused_vs_rounds": round(min(ms_f) / min(ms), 4) if has_fused else None,
+                                "fused_vs_uniform": round(min(ms_f) / min(ms_u), 4) if has_fused else None,
                                 "waves_histogram": {int(v): int(c) for v, c in zip(vals, counts)},
                                 "tile_error": {"max": float(err.max()), "mean": float(err.mean())},
                                 "vs_uniform_plain": round(min(ms) / min(uni["plain"]), 4)})

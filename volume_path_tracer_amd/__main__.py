@@ -8,7 +8,8 @@ convert the film to 8-bit sRGB (film_to_image) and save a PNG.
 reference's volumes are not shipped).  ``--spp`` overrides num_waves; ``--size WxH`` overrides
 output_size.  ``--adaptive ERR`` renders until every tile's error estimate is at most ERR
 (render.render_adaptive): ``--spp`` becomes the cap, ``--min-spp`` / ``--spp-step`` the first round and
-the later rounds' waves, ``--waves-out`` saves the per-tile wave map.  Exits 1 on a fatal error, like
+the later rounds' waves, ``--waves-out`` saves the per-tile wave map, ``--adaptive-fused`` runs the
+one-launch driver (the same bytes).  Exits 1 on a fatal error, like
 vptFATAL.
 """
 from __future__ import annotations
@@ -44,6 +45,8 @@ def main(argv=None) -> int:
                     help="adaptive sampling: render each tile until its error estimate is <= ERR (--spp is the cap)")
     ap.add_argument("--min-spp", type=int, default=64, help="adaptive: waves of the first round")
     ap.add_argument("--spp-step", type=int, default=64, help="adaptive: waves per later round")
+    ap.add_argument("--adaptive-fused", action="store_true",
+                    help="adaptive: the one-launch driver (vpt_gpu_render_adaptive_fused; tiles of at most 256 pixels)")
     ap.add_argument("--waves-out", default=None, help="adaptive: save the per-tile wave map (.npy, uint32[T])")
     args = ap.parse_args(argv)
 
@@ -76,9 +79,12 @@ def main(argv=None) -> int:
         t0 = time.perf_counter()
         if args.adaptive is not None:
             film, waves, err, info = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
-                                                     step_waves=args.spp_step, max_waves=cfg.num_waves)
+                                                     step_waves=args.spp_step, max_waves=cfg.num_waves,
+                                                     fused=args.adaptive_fused)
             ms = (time.perf_counter() - t0) * 1e3
-            print(f"[vpt] Adaptive rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, target {args.adaptive:g}, "
+            driver = "one launch (fused)" if args.adaptive_fused else "rounds"
+            print(f"[vpt] Adaptive rendering ({driver} driver) complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, "
+                  f"target {args.adaptive:g}, "
                   f"{int(waves.min())}-{int(waves.max())} spp): {info['jobs_rendered']} of {info['jobs_uniform']} jobs "
                   f"({info['jobs_rendered'] / info['jobs_uniform']:.3f}), {info['rounds']} rounds, "
                   f"{info['tiles_at_max']} tiles at the cap, max tile error {info['max_error']:.4g}", file=sys.stderr)

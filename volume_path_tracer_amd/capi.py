@@ -261,6 +261,9 @@ def lib() -> C.CDLL:
         L.vpt_gpu_tile_errors.argtypes = [vp, vp, vp, C.c_float, fp, vp]
         L.vpt_gpu_render_adaptive.argtypes = [vp, C.POINTER(AdaptiveParams), vp, vp, C.POINTER(C.c_uint32), fp,
                                               C.POINTER(AdaptiveResult), vp]
+    if hasattr(L, "vpt_gpu_render_adaptive_fused"):
+        L.vpt_gpu_render_adaptive_fused.argtypes = [vp, C.POINTER(AdaptiveParams), vp, vp, C.POINTER(C.c_uint32), fp,
+                                                    C.POINTER(AdaptiveResult), vp]
     L.vpt_gpu_sync.argtypes = [vp]
     L.vpt_gpu_film_clear.argtypes = [vp]
     L.vpt_gpu_film_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]

@@ -162,6 +162,12 @@ struct vpt_gpu_ctx {
   // passes while attached.  tile_err: vpt_gpu_tile_errors' T results (device, allocated with band_rank).
   float* m2 = nullptr;
   float* tile_err = nullptr;
+  // Gang launches (vpt_gpu_render_adaptive_fused): the wavefronts' sample scratch (wavefronts x tile_area x 64 x 3
+  // floats, grown when the grid does) and the tiles' wave counts (T words; their errors go to tile_err).  Allocated
+  // by the first call, freed with the context.
+  float* gang_scratch = nullptr;
+  uint64_t gang_scratch_bytes = 0;
+  uint32_t* gang_waves = nullptr;
   // The drop-in's ordered frame (vpt_gpu_frame_open / _finish): its feed launches also store the samples of the
   // frame's tiles [frame_tile_lo, + frame_tiles) from job frame_jid_lo on into the sample buffer above, frame_waves
   // waves of those tiles (0: no frame open); the order pass writes frame_film (device, film_count floats), copied

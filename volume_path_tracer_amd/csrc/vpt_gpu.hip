@@ -191,6 +191,8 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->list_dev);
   (void)hipFree(ctx->list_slot_dev);
   (void)hipFree(ctx->tile_err);
+  (void)hipFree(ctx->gang_scratch);
+  (void)hipFree(ctx->gang_waves);
   (void)hipFree(ctx->perm);
   (void)hipFree(ctx->samples);
   (void)hipFree(ctx->frame_film);
@@ -1086,6 +1088,99 @@ int vpt_gpu_render_adaptive(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p, floa
     if (waves_T_host[t] >= p->max_waves) ++res.tiles_at_max;
     res.max_error = std::max(res.max_error, err_T_host[t]);
   }
+  if (out) *out = res;
+  return VPT_OK;
+}
+
+int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p, float* film_device, float* m2_device,
+                                  uint32_t* waves_T_host, float* err_T_host, vpt_adaptive_result* out, void* hip_stream) {
+  if (!ctx || !p || !m2_device || !waves_T_host || !err_T_host)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive_fused: null argument");
+  if (p->min_waves < 2 || p->step_waves == 0 || p->max_waves < p->min_waves || !(p->target_error >= 0.0f) ||
+      !(p->abs_floor > 0.0f))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive_fused: needs min_waves >= 2, step_waves >= 1, max_waves "
+                                         ">= min_waves, target_error >= 0 and abs_floor > 0");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->scene.pixel_mode)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive_fused: gang launches run the reference RNG mode");
+  if (ctx->scene.tile_area > vpt::kGangMaxArea)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive_fused: tiles of more than " + std::to_string(vpt::kGangMaxArea) +
+                                             " pixels are not supported (the error tree is held in registers); "
+                                             "vpt_gpu_render_adaptive renders them");
+  if (ctx->film_order != VPT_FILM_ORDERED)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: gang launches need the ordered film "
+                                       "(vpt_gpu_set_film_order: VPT_FILM_ORDERED)");
+  if (ctx->frame_waves)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: a frame is open (its launches add with film atomics)");
+  if (ctx->open_feeds.load() > 0)  // (the call allocates and waits for its launch, which would wait for the feed's)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: a feed of this context is open");
+  const uint32_t T = (uint32_t)ctx->scene.T;
+  if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks; allocates tile_err with them)
+  // The full resident grid of the throughput kernel; every wavefront has a scratch slot of one group's samples.
+  const uint32_t blocks = (uint32_t)ctx->grid_blocks;
+  const uint64_t bytes = (uint64_t)blocks * vpt::kBlockThreads * ctx->scene.tile_area * 3 * sizeof(float);
+  if (ctx->gang_scratch_bytes < bytes) {
+    (void)hipFree(ctx->gang_scratch);
+    ctx->gang_scratch = nullptr;
+    ctx->gang_scratch_bytes = 0;
+    const hipError_t e = hipMalloc((void**)&ctx->gang_scratch, bytes);
+    if (e != hipSuccess) {
+      ctx->gang_scratch = nullptr;
+      (void)hipGetLastError();
+      return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_adaptive_fused: " + std::to_string(bytes >> 20) +
+                                             " MiB of wavefront scratch: " + hipGetErrorString(e));
+    }
+    ctx->gang_scratch_bytes = bytes;
+  }
+  if (!ctx->gang_waves) VPT_HIP(hipMalloc((void**)&ctx->gang_waves, (size_t)T * sizeof(uint32_t)));
+  if (!ctx->tile_err) return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_adaptive_fused: no tile-error buffer (its allocation failed)");
+  hipStream_t s = (hipStream_t)hip_stream;
+  vpt::KernelArgs env{};
+  env.jid_begin = 0;
+  env.jid_count = T;  // (work items: the tiles)
+  env.pixel_chunk = 1;
+  env.film = film_device ? film_device : ctx->film;
+  env.tile_area = ctx->scene.tw * ctx->scene.th;
+  env.prof_buf = ctx->prof;
+  env.order = ctx->order;
+  env.order_group = 1;
+  env.gang_scratch = ctx->gang_scratch;
+  env.gang_m2 = m2_device;  // (the context's attachment is neither used nor changed)
+  env.gang_waves = ctx->gang_waves;
+  env.gang_err = ctx->tile_err;
+  env.gang_target = p->target_error;
+  env.gang_floor = p->abs_floor;
+  env.gang_min = p->min_waves;
+  env.gang_step = p->step_waves;
+  env.gang_max = p->max_waves;
+  uint32_t slot = 0;
+  if ((rc = take_slot(ctx, s, slot))) return rc;
+  env.job_counter = ctx->job_counter + 2 * slot;
+  env.event_count = ctx->job_counter + 2 * slot + 1;
+  const bool temp = ctx->scene.has_temperature != 0;
+  auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, false, true>
+                     : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, false, true>
+                                     : vpt::vpt_integrate_kernel<false, false, false, false, false, false, false, true>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, ctx->scene_full_dev, ctx->counters);
+  ctx->last_gate_set = VPT_GATES_FULL;
+  VPT_HIP(hipGetLastError());
+  ++ctx->ordered_launches;
+  VPT_HIP(hipMemcpyAsync(waves_T_host, ctx->gang_waves, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  VPT_HIP(hipMemcpyAsync(err_T_host, ctx->tile_err, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, s));
+  if ((rc = release_slot(ctx, s, slot))) return rc;
+  VPT_HIP(hipStreamSynchronize(s));
+  vpt_adaptive_result res{};
+  res.jobs_uniform = (uint64_t)p->max_waves * T;
+  uint32_t longest = p->min_waves;
+  for (uint32_t t = 0; t < T; ++t) {
+    res.jobs_rendered += waves_T_host[t];
+    longest = std::max(longest, waves_T_host[t]);
+    if (waves_T_host[t] >= p->max_waves) ++res.tiles_at_max;
+    res.max_error = std::max(res.max_error, err_T_host[t]);
+  }
+  // round 0 and the later boundaries the longest-running tile crossed: the rounds driver's count
+  res.rounds = 1 + (uint32_t)(((uint64_t)(longest - p->min_waves) + p->step_waves - 1) / p->step_waves);
   if (out) *out = res;
   return VPT_OK;
 }

@@ -1157,6 +1157,30 @@ __host__ __device__ __forceinline__ uint64_t band_sample_floats(uint32_t tiles, 
   return (uint64_t)tiles * band_groups(waves, G) * tile_area * G * 3;
 }
 
+// The walk state of a lane between two jobs, reset (a gang launch's fetch; every field is set again by begin_ray).
+__host__ __device__ __forceinline__ void lane_park(Lane& ln) {
+  ln.sm = SM_NONE;
+  ln.shadow = 0;
+  for (int i = 0; i < 3; ++i) {
+    ln.e[i] = ln.d[i] = ln.nxt[i] = ln.finc[i] = 0.0f;
+    ln.vox[i] = ln.vinc[i] = 0;
+  }
+  ln.scale = ln.rscale = ln.maj = ln.Tn = ln.T1 = ln.s_t0 = ln.s_t1 = ln.s_dmaj = 0.0f;
+  ln.dim = 0;
+  ln.pw = 0;
+}
+
+// Env::kGang, false for an environment without one (gang launches, vpt_gpu_render_adaptive_fused: the kernel's
+// KernelEnvT<.., Gang>; every other environment compiles lane_iteration's gang fetch out).
+template <class Env, class = void>
+struct env_is_gang {
+  static constexpr bool value = false;
+};
+template <class Env>
+struct env_is_gang<Env, decltype((void)Env::kGang)> {
+  static constexpr bool value = Env::kGang;
+};
+
 // ------------------------------------------------------------------------------------------------
 // One iteration of the lane loop.  Env supplies fetch_job(uint64_t& item, wave_lanes) -> bool, jid_begin, the
 // job order (order == nullptr: item k is job jid_begin + k; else ordered_job()),
@@ -1252,6 +1276,39 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
     const DevScene S = *opaque(sp);
     const DevGrid& G = S.density;
     (void)G;
+    if constexpr (env_is_gang<Env>::value) {
+      // A gang launch: the wavefront owns a tile and fetches as one -- only when all 64 lanes are parked here (lanes
+      // beyond the group and lanes whose job is done wait in ST_FETCH; n_fetch >= gate_min would run the block for them
+      // every pass).  env.gang_next closes the group just rendered and deals the next one, or ends every lane at once.
+      if (env.count(ln.state == ST_FETCH) == 64) {
+        env.prof(PB_FETCH);
+        uint64_t jid;
+        uint32_t tile;
+        const int got = env.gang_next(S, jid, tile);
+        // Every lane is between two jobs: its ray and HDDA state is dead (begin_ray sets all of it).  Saying so keeps
+        // those registers free for the close instead of spilling them around it.
+        lane_park(ln);
+        if (got == 0) {
+          ln.state = ST_DONE;
+          return;
+        }
+        if (got > 0) {
+#ifdef VPT_JOB_LOG
+          lc.job = (uint32_t)jid;
+          lc.t_start = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
+          ln.rng = job_seed(S.seed, jid);
+          lc.x0 = (int32_t)(tile % S.ntx) * S.tw;  // TileProvider::compute_tile_rect
+          lc.y0 = (int32_t)(tile / S.ntx) * S.th;
+          lc.pix = 0;
+          if (HasTemp) {
+            ln.temp_cell.i = kNoCell;
+            ln.temp_cell.code = -1;
+          }
+          ln.state = ST_PIXEL;
+        }
+      }
+    } else {
     // (a feed lane holding an unread item runs the block at once: its ring slot is pinned until it reads it)
     const int32_t n_fetch = env.count(ln.state == ST_FETCH);
     if (n_fetch > 0 && (starving || n_fetch >= gate_min || env.fetch_urgent(ln.state == ST_FETCH)) &&
@@ -1303,6 +1360,7 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
         ln.temp_cell.code = -1;
       }
       ln.state = ST_PIXEL;
+    }
     }
   }
   env.tick(PT_FETCH);

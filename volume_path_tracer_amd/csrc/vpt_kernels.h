@@ -99,6 +99,18 @@ struct KernelArgs {
   // A tile-list launch (vpt_gpu_render_tile_list): a band launch whose tiles are a list; tile t's index in the list
   // (the tb of band_slot) is band_slot_map[t].  nullptr: a contiguous band, tb = t - band_tile_lo.
   const uint32_t* band_slot_map;
+  // A gang launch (vpt_gpu_render_adaptive_fused; the kernels' Gang instantiations only): a wavefront owns a tile.  It
+  // claims tiles order[job_counter++] (descending cost) until jid_count = T are taken, renders the tile's waves in
+  // groups of up to 64 (one per lane) into its slot of gang_scratch ([wavefront][lane][tile_area][3] floats), adds
+  // each group into film and gang_m2 in wave order itself, and at the boundaries gang_min, + gang_step .., gang_max
+  // evaluates the tile's error estimate: it goes on while err > gang_target (or gang_target == 0) below gang_max,
+  // else stores gang_waves[tile], gang_err[tile] and claims again (KernelEnvT::gang_next).
+  float* gang_scratch;
+  float* gang_m2;
+  uint32_t* gang_waves;
+  float* gang_err;
+  float gang_target, gang_floor;
+  uint32_t gang_min, gang_step, gang_max;
 };
 typedef const __attribute__((address_space(4))) KernelArgs* ArgsPtr;
 // This workgroup's event counters and (VPT_PROFILE builds) section cycles; the temperature kernel's LDS copy of
@@ -110,6 +122,11 @@ __shared__ unsigned long long g_wg_prof[PT_COUNT + kBlockThreads / 64];
 __shared__ float g_bb_lds[kBbFloats];
 // A finish-block pass's samples, per wavefront by rank: (pixel index << 6) | lane (KernelEnvT::film_add / film_commit).
 __shared__ uint32_t g_film_rank[kBlockThreads];
+// A gang launch's per-wavefront state: the tile it owns, the tile's waves added to the film, the next boundary and
+// the size of the group being rendered (0: none, the wavefront claims a tile at its next fetch).
+__shared__ uint32_t g_gang[kBlockThreads / 64][4];
+// The largest tile of a gang launch: the error tree's lane-local levels hold four values per lane.
+constexpr uint32_t kGangMaxArea = 256;
 
 // The kernel's view of its launch.  RegCold: the latency kernel's (the lane's cold state in VGPRs).  Feed: a feed
 // launch's (job ids from the host's ring, fetch_feed); other launches compile the feed protocol out.  The
@@ -118,10 +135,14 @@ __shared__ uint32_t g_film_rank[kBlockThreads];
 // in SGPRs across the state-machine loop (they spilled to VGPR lanes: v_readlane / v_writelane in every block).
 // Band: a band launch's (vpt_gpu_render_tiles): its own item -> job mapping and sample layout, read in fetch_job,
 // job_start and film_add only; every other launch compiles them out.
-template <bool RegCold, bool Feed = false, bool Band = false>
+// Gang: a gang launch's (vpt_gpu_render_adaptive_fused): the wavefront's fetch is gang_next, film_add stores into the
+// wavefront's scratch; every other launch compiles them out.
+template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false>
 struct KernelEnvT {
   static_assert(!(RegCold && Feed), "feeds run the throughput kernels only");
   static_assert(!(Band && Feed), "band launches are no feeds");
+  static_assert(!(Gang && (RegCold || Feed || Band)), "gang launches run the plain throughput kernels only");
+  static constexpr bool kGang = Gang;  // (lane_iteration's fetch block)
   __device__ __forceinline__ ArgsPtr args() const {
     ArgsPtr p = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();  // (KernelArgs is the first argument: offset 0)
     asm volatile("" : "+s"(p));
@@ -392,7 +413,7 @@ struct KernelEnvT {
   // A band launch stores from the lane too, at its job's address (job_start) + pixel * band_group * 3 floats: under
   // the same-tile order the wavefront's lanes are consecutive waves of one tile, whose samples of a pixel are adjacent.
   __device__ __forceinline__ bool film_regroup(const DevScene& S) const {
-    if constexpr (Band) return false;
+    if constexpr (Band || Gang) return false;
     if (args()->samples) return false;
     return !RegCold && (args()->samples != nullptr || (uint64_t)S.W * (uint64_t)S.H < (1ULL << 26));  // (index << 6 | lane fits 32 bits)
   }
@@ -402,6 +423,17 @@ struct KernelEnvT {
       (void)ln;
       float* s = reinterpret_cast<float*>(((uint64_t)lc.item_hi << 32) | lc.item_lo) +
                  (uint64_t)(uint32_t)((py - lc.y0) * rw + (px - lc.x0)) * (args()->band_group * 3u);
+      s[0] = lc.L[0];
+      s[1] = lc.L[1];
+      s[2] = lc.L[2];
+      return;
+    }
+    if constexpr (Gang) {  // the lane's slot of the wavefront's scratch: [lane][pixel][3]
+      (void)ln;
+      uint32_t tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));  // (else the slot's base is hoisted out of the state-machine loop into VGPRs)
+      float* s = args()->gang_scratch +
+                 ((uint64_t)(blockIdx.x * kBlockThreads + tid) * S.tile_area + (uint32_t)((py - lc.y0) * rw + (px - lc.x0))) * 3u;
       s[0] = lc.L[0];
       s[1] = lc.L[1];
       s[2] = lc.L[2];
@@ -446,6 +478,138 @@ struct KernelEnvT {
       rec[2] = lc.L[2];
     }
   }
+  // ---- gang launches (vpt_gpu_render_adaptive_fused) ----
+  // The close of a group: every lane of the wavefront is parked and active.  In chunks of 64 pixels lane p adds the
+  // group's g samples of pixel 64 c + p into the film's float4 and the plane in wave order -- w += 1, x += r Lx,
+  // y' = r Ly, y += y', z += r Lz, m += y' y', vpt_band_order_kernel<true>'s sequence -- reading the scratch's
+  // [lane k][pixel] rows (one instruction: 64 x 12 adjacent bytes).  Ragged tiles' missing pixels and, in
+  // single-pixel mode, every other pixel are not touched.  boundary: also the tile's error estimate from the values
+  // just written, vpt_tile_error_kernel's arithmetic and tree: pixel q = l + 64 c is in lane l, so the levels h >= 64
+  // of a[i] += a[i + h] add a lane's own values (chunks 0 + 2 and 1 + 3, then 0 + 1) and the levels 32 .. 1 fetch
+  // lane i + h's; the +0.0 padding up to P is added as there.  Returns the estimate (uniform; 0 unless boundary).
+  __device__ __forceinline__ float gang_close(const DevScene& S, uint32_t tile, uint32_t g, bool boundary, uint32_t tid) {
+    const ArgsPtr A = args();
+    const uint32_t l = tid & 63u, area = S.tile_area;
+    uint32_t P = 1;
+    while (P < area) P <<= 1;
+    const int32_t x0 = (int32_t)(tile % S.ntx) * S.tw, y0 = (int32_t)(tile / S.ntx) * S.th;
+    const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
+    const float r = S.imaging_ratio;
+    const float* const rows = A->gang_scratch + (uint64_t)(blockIdx.x * kBlockThreads + (tid & ~63u)) * area * 3u;
+    float* const film = A->film;
+    float* const m2 = A->gang_m2;
+    float se0 = 0.0f, se1 = 0.0f, mu0 = 0.0f, mu1 = 0.0f;
+    uint32_t cnt = 0;
+#pragma unroll 1
+    for (uint32_t c = 0; c * 64u < P; ++c) {  // (uniform)
+      const uint32_t q = c * 64u + l;
+      bool mine = q < area && (int32_t)q < rw * rh;
+      const int32_t yl = div_pix((int32_t)q, rw), px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
+      if (S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) mine = false;  // (no sample: worker.cpp:113-116)
+      float e = 0.0f, mu = 0.0f;
+      bool counted = false;
+      if (mine) {
+        const uint64_t p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
+        float4* const f = reinterpret_cast<float4*>(film) + p;
+        float4 a = *f;
+        float m = m2[p];
+        const float* s = rows + (uint64_t)q * 3u;
+#pragma unroll 4
+        for (uint32_t k = 0; k < g; ++k, s += (uint64_t)area * 3u) {  // (in wave order, never reduced across waves)
+          const float y = r * s[1];
+          a.w = a.w + 1.0f;
+          a.x = a.x + r * s[0];
+          a.y = a.y + y;
+          a.z = a.z + r * s[2];
+          m = m + y * y;
+        }
+        *f = a;
+        m2[p] = m;
+        const float n = a.w;
+        if (boundary && n >= 2.0f) {
+          mu = a.y / n;
+          const float ex2 = m / n;
+          float v = ex2 - mu * mu;
+          if (!(v > 0.0f)) v = 0.0f;
+          e = sqrtf(v / (n - 1.0f));
+          counted = true;
+        }
+      }
+      cnt += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(counted));
+      se0 = c == 0 ? e : (c == 2 ? se0 + e : se0);
+      mu0 = c == 0 ? mu : (c == 2 ? mu0 + mu : mu0);
+      se1 = c == 1 ? e : (c == 3 ? se1 + e : se1);
+      mu1 = c == 1 ? mu : (c == 3 ? mu1 + mu : mu1);
+    }
+    if (!boundary) return 0.0f;
+    if (P >= 128u) {  // h = 64
+      se0 = se0 + se1;
+      mu0 = mu0 + mu1;
+    }
+    for (uint32_t h = min(32u, P >> 1); h >= 1; h >>= 1) {  // (uniform; every lane active: lane i < h adds lane i + h's)
+      se0 = se0 + __shfl_down(se0, h);
+      mu0 = mu0 + __shfl_down(mu0, h);
+    }
+    const float err = cnt ? se0 / (mu0 + A->gang_floor * (float)cnt) : 0.0f;  // (lane 0's is the tile's)
+    return __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, err)));
+  }
+  // The wavefront's fetch, run when all 64 lanes are parked in ST_FETCH (no lane ever leaves the loop alone: lane p
+  // owns pixel p in the close).  Closes the group just rendered, if any; at a boundary decides with the host
+  // driver's comparison whether the tile goes on; else (or without a tile) claims the next one.  Then deals the next
+  // group: lane l < g = min(64, boundary - done) gets job (done + l) * T + tile (1; its id in jid), the others stay
+  // parked (-1).  0, for all lanes at once: no tile is left.
+  __device__ __forceinline__ int gang_next(const DevScene& S, uint64_t& jid, uint32_t& tile_out) {
+    const ArgsPtr A = args();
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const uint32_t l = tid & 63u;
+    uint32_t* const st = g_gang[tid >> 6];
+    uint32_t tile = __builtin_amdgcn_readfirstlane(st[0]), done = __builtin_amdgcn_readfirstlane(st[1]),
+             b = __builtin_amdgcn_readfirstlane(st[2]), g = __builtin_amdgcn_readfirstlane(st[3]);
+    const uint32_t cap = A->gang_max;
+    if (g != 0) {
+      // The samples were stored by this wavefront's other lanes, on this CU: release, then acquire, at workgroup scope.
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      const bool boundary = done + g == b;
+      const float err = gang_close(S, tile, g, boundary, tid);
+      done += g;
+      g = 0;
+      bool go_on = !boundary;
+      if (boundary) {
+        const float target = A->gang_target;
+        go_on = (target == 0.0f || err > target) && done < cap;  // (target 0: no tile ever stops)
+        if (go_on) {
+          b = cap - b < A->gang_step ? cap : b + A->gang_step;
+        } else if (l == 0) {
+          A->gang_waves[tile] = done;
+          A->gang_err[tile] = err;
+        }
+      }
+      if (!go_on) tile = 0xffffffffu;
+    }
+    if (tile == 0xffffffffu) {
+      uint32_t i = 0;
+      if (l == 0) i = (uint32_t)min(atomicAdd(A->job_counter, 1ULL), (unsigned long long)0xffffffffu);
+      i = __builtin_amdgcn_readfirstlane(i);
+      if (i >= (uint32_t)A->jid_count) return 0;
+      tile = __builtin_amdgcn_readfirstlane(A->order[i]);
+      done = 0;
+      b = A->gang_min;
+    }
+    g = min(64u, b - done);
+    if (l == 0) {
+      st[0] = tile;
+      st[1] = done;
+      st[2] = b;
+      st[3] = g;
+    }
+    if (l >= g) return -1;
+    tile_out = tile;
+    jid = (uint64_t)(done + l) * S.T + tile;
+    return 1;
+  }
+
   // fin: this lane ran film_add in the pass just ended.  Called by every lane still in the loop; the lanes that
   // have left it (their jobs done) are not there to add, so the 3 n adds go to the active lanes by rank, as many
   // per wave-instruction as there are active lanes (adds 3k, 3k + 1, 3k + 2: sample k's X, Y, Z).
@@ -613,7 +777,8 @@ __device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc
 }
 
 // counters[] order = vpt_counters field order
-template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false>
+template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false,
+          bool Gang = false>
 __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT : (Debug ? VPT_WAVES_SLOW : (HasTemp ? VPT_WAVES_TEMP : VPT_WAVES_FAST)))) void vpt_integrate_kernel(KernelArgs args, const DevScene* scene,
                                                                        unsigned long long* counters) {
   (void)args;  // read through KernelEnvT::args()
@@ -630,7 +795,15 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
   if (threadIdx.x % 64 == 0) g_wg_prof[PT_COUNT + threadIdx.x / 64] = clock64();
 #endif
   static_assert(!(Band && Debug), "band launches have no records or events");
-  KernelEnvT<Lat, Feed, Band> env;
+  static_assert(!(Gang && (Debug || Lat || Compact || Feed || Band)), "gang launches run the plain throughput kernels only");
+  if constexpr (Gang) {
+    if (threadIdx.x < kBlockThreads / 64) {  // no tile, no group (read by the wavefront itself: no barrier needed)
+      g_gang[threadIdx.x][0] = 0xffffffffu;
+      g_gang[threadIdx.x][3] = 0;
+    }
+    __syncthreads();
+  }
+  KernelEnvT<Lat, Feed, Band, Gang> env;
   env.reg_cold = nullptr;
   Lane ln;
   lane_init(ln);

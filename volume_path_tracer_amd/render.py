@@ -500,11 +500,12 @@ def run(cfg: capi.Configuration, integrator: Integrator, tp: TileProvider, film:
 
 
 def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, step_waves: int = 64,
-                    max_waves: Optional[int] = None, abs_floor: float = 1e-3):
+                    max_waves: Optional[int] = None, abs_floor: float = 1e-3, fused: bool = False):
     """Render a frame from zero until every tile's error estimate (Integrator.tile_errors) is at most
     `target_error` or it has `max_waves` waves (None: cfg.num_waves): `min_waves` waves of every tile, then
     `step_waves` more per round of the tiles still above the target (vpt_gpu_render_adaptive).  Each tile's film
-    is the uniform frame's after its own wave count, bit for bit.
+    is the uniform frame's after its own wave count, bit for bit.  fused: the one-launch driver
+    (vpt_gpu_render_adaptive_fused: a wavefront owns a tile; the same bytes; tiles of at most 256 pixels).
     -> (film float32[H][W][4], waves uint32[T], err float32[T], info dict)."""
     torch = it.torch
     T = it.cfg.jobs_per_wave()
@@ -515,10 +516,11 @@ def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, st
                             int(it.cfg.num_waves if max_waves is None else max_waves))
     res = capi.AdaptiveResult()
     waves, err = np.zeros(T, np.uint32), np.zeros(T, np.float32)
-    capi.check(capi.lib().vpt_gpu_render_adaptive(it.h, C.byref(p), C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
-                                                  waves.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res),
-                                                  C.c_void_p(it.stream_handle(None))), "vpt_gpu_render_adaptive")
+    name = "vpt_gpu_render_adaptive_fused" if fused else "vpt_gpu_render_adaptive"
+    capi.check(getattr(capi.lib(), name)(it.h, C.byref(p), C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                         waves.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res),
+                                         C.c_void_p(it.stream_handle(None))), name)
     return film.cpu().numpy(), waves, err, res.as_dict()
 
 
