@@ -278,6 +278,9 @@ def cube_od(o, d, ta, tb):
     return tau
 
 
+HG_ISOTROPIC_BELOW = 1e-3   # sample_henyey_greenstein's isotropic branch: |g| < 1e-3 (random.hpp:62)
+
+
 def hg_reference(cos_wwi, g):
     """henyey_greenstein(w.dot(wi), g) as the reference evaluates it in NEE: den = 1 + g^2 + 2 g c with
     the FORWARD ray direction w (utils.hpp:61-66, worker.cpp:88) -- pbrt's phase with the sign mirrored."""
@@ -288,10 +291,21 @@ def hg_reference(cos_wwi, g):
 def hg_cos_cdf(mu, g):
     """CDF of cos(theta) between the incoming direction w and the sampled one under
     sample_henyey_greenstein (random.hpp:56-84): local z = w and cos = (1 + g^2 - ((1 - g^2) /
-    (1 + g - 2 g u))^2) / (2 g), i.e. p(mu) = (1 - g^2) / (2 (1 + g^2 - 2 g mu)^1.5), forward-peaked
-    (mean g) for g > 0."""
+    (1 + g - 2 g u))^2) / (2 g), i.e. p(mu) = (1 - g^2) / (2 (1 + g^2 - 2 g mu)^1.5), mean g: forward-peaked
+    for g > 0, backward-peaked for g < 0 (the same formula: sqrt((1 + g)^2) = 1 + g for g > -1).  For
+    |g| < 1e-3 the reference samples isotropically, cos = 1 - 2 u (random.hpp:62-63): the CDF is linear."""
     mu = np.asarray(mu, np.float64)
+    if abs(g) < HG_ISOTROPIC_BELOW:
+        return 0.5 * (mu + 1.0)
     return (1.0 - g * g) / (2.0 * g) * (1.0 / np.sqrt(1.0 + g * g - 2.0 * g * mu) - 1.0 / (1.0 + g))
+
+
+def hg_sample_cos(g, u):
+    """cos(theta) of sample_henyey_greenstein for the uniform number u (random.hpp:60-68), float64."""
+    u = np.asarray(u, np.float64)
+    if abs(g) < HG_ISOTROPIC_BELOW:
+        return 1.0 - 2.0 * u
+    return (1.0 + g * g - ((1.0 - g * g) / (1.0 + g - 2.0 * g * u)) ** 2) / (2.0 * g)
 
 
 def single_scatter(o, w, wi, sigma_s, sub=48, npts=8, t_shadow0=1e-5):
@@ -349,10 +363,9 @@ def max_scatters(max_depth):
 
 def hg_sample_dirs(d, g, u1, u2):
     """sample_henyey_greenstein (random.hpp:56-84) about the incoming directions d [n, 3]: local z = d,
-    cos = (1 + g^2 - ((1 - g^2) / (1 + g - 2 g u1))^2) / (2 g), phi = 2 pi u2 (any frame about d: the law
-    is symmetric in phi)."""
-    cos = (1.0 + g * g - ((1.0 - g * g) / (1.0 + g - 2.0 * g * u1)) ** 2) / (2.0 * g)
-    cos = np.clip(cos, -1.0, 1.0)
+    cos = (1 + g^2 - ((1 - g^2) / (1 + g - 2 g u1))^2) / (2 g) (1 - 2 u1 for |g| < 1e-3: hg_sample_cos),
+    phi = 2 pi u2 (any frame about d: the law is symmetric in phi)."""
+    cos = np.clip(hg_sample_cos(g, u1), -1.0, 1.0)
     sin = np.sqrt(np.maximum(0.0, 1.0 - cos * cos))
     a = np.where(np.abs(d[:, :1]) < 0.9, [[1.0, 0.0, 0.0]], [[0.0, 1.0, 0.0]])
     e1 = np.cross(d, a)

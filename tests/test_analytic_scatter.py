@@ -47,10 +47,10 @@ WI = (0.3, 0.5, -0.8)          # distant light inv_direction (toward the light):
 INDEX_OF_WORLD = 64.0          # the cube's map: world = index - 64
 
 
-def scatter_config(w, h, spp):
+def scatter_config(w, h, spp, g=G):
     wl = workload("c2", width=w, height=h, spp=spp)
     v = wl.cfg.volume_parameters
-    v.sigma_s, v.sigma_a, v.henyey_greenstein_g = SIGMA_S, 0.0, G
+    v.sigma_s, v.sigma_a, v.henyey_greenstein_g = SIGMA_S, 0.0, g
     p = wl.cfg.worker_parameters
     p.max_depth = 2
     p.use_jitter = 0
@@ -154,9 +154,11 @@ def sampling_report(ev, g):
             "ok": bool(mu.size >= 5000 and p_mu > 1e-3 and p_phi > 1e-3)}
 
 
-def sampling_config(w=16, h=16, spp=4):
-    """C2's cube as BASELINE runs it (sigma_s 0.15, g 0.4, max_depth 100): tens of scatters per path."""
+def sampling_config(w=16, h=16, spp=4, g=G):
+    """C2's cube as BASELINE runs it (sigma_s 0.15, max_depth 100; g 0.4 unless given): tens of scatters per
+    path."""
     wl = workload("c2", width=w, height=h, spp=spp)
+    wl.cfg.volume_parameters.henyey_greenstein_g = g
     return wl
 
 
@@ -192,44 +194,60 @@ def test_single_scatter_integral_matches_brute_force():
         assert abs(I[i] - ref) < 1e-6 * max(1.0, ref), (i, I[i], ref)
 
 
-def test_hg_cdf_is_the_sampler_law():
-    """hg_cos_cdf inverts the reference's cos(theta) formula: F(cos(u)) = 1 - u."""
+@pytest.mark.parametrize("g", [0.4, -0.4, 0.95, 5e-4])
+def test_hg_cdf_is_the_sampler_law(g):
+    """hg_cos_cdf inverts the reference's cos(theta) formula (random.hpp:62-65, written out here): F(cos(u)) =
+    1 - u, for forward and backward peaks and on the isotropic branch (|g| < 1e-3: cos = 1 - 2 u)."""
     u = np.linspace(0.0, 1.0, 101)
-    cos = (1 + G * G - ((1 - G * G) / (1 + G - 2 * G * u)) ** 2) / (2 * G)
-    np.testing.assert_allclose(A.hg_cos_cdf(cos, G), 1.0 - u, atol=1e-12)
+    if abs(g) < 1e-3:
+        cos = 1 - 2 * u
+    else:
+        cos = (1 + g * g - ((1 - g * g) / (1 + g - 2 * g * u)) ** 2) / (2 * g)
+    np.testing.assert_allclose(A.hg_cos_cdf(cos, g), 1.0 - u, atol=1e-12)
+    np.testing.assert_allclose(A.hg_sample_cos(g, u), cos, atol=1e-15)
 
 
 # ---- the oracle --------------------------------------------------------------------------------------
 ORACLE_SHAPE = (24, 24, 16, 32)      # width, height, batches K, spp per batch
 
 
-def oracle_batches(mutant=0):
+def oracle_batches(mutant=0, g=G):
     w, h, K, spp_b = ORACLE_SHAPE
-    wl = scatter_config(w, h, K * spp_b)
+    wl = scatter_config(w, h, K * spp_b, g)
     od = O.OracleGrid(SynthGrid(0, 128).grid(), fix_majorants=True, L=O.lib(mutant))
     T = wl.cfg.jobs_per_wave()
     films = np.stack([O.render_jobs(wl.cfg, od, None, k * spp_b * T, spp_b * T)[0] for k in range(K)])
     return wl.cfg, films
 
 
-def oracle_events(mutant=0):
-    wl = sampling_config()
+def oracle_events(mutant=0, g=G):
+    wl = sampling_config(g=g)
     od = O.OracleGrid(SynthGrid(0, 128).grid(), fix_majorants=True, L=O.lib(mutant))
     ev, _ = O.render_jobs_events(wl.cfg, od, None, 0, wl.cfg.jobs_per_wave() * wl.spp, capacity=1 << 21)
     return ev
 
 
-def test_oracle_single_scatter_matches_analytic():
-    cfg, films = oracle_batches()
+# The NEE weight away from g = 0.4: the isotropic phase (1 / 4 pi) and, with w . wi ~ -0.8, g = -0.6 on the strongly
+# peaked side of the reference's mirrored HG (den = 1 + g^2 + 2 g w . wi ~ 0.4).
+SCATTER_G = [0.4, 0.0, -0.6]
+# The sampling law: forward and backward peaks, the isotropic branch, a sharp peak.
+SAMPLING_G = [0.4, 0.0, -0.4, 0.95]
+
+
+@pytest.mark.parametrize("g", SCATTER_G)
+def test_oracle_single_scatter_matches_analytic(g):
+    cfg, films = oracle_batches(g=g)
     rep = scatter_report(cfg, films)
     assert rep["ok"], rep
     assert rep["pixels"] >= 300
 
 
-def test_oracle_hg_sampling_law():
-    rep = sampling_report(oracle_events(), G)
+@pytest.mark.parametrize("g", SAMPLING_G)
+def test_oracle_hg_sampling_law(g):
+    """g = 0: the isotropic law (mean cos 0, cos uniform on [-1, 1])."""
+    rep = sampling_report(oracle_events(g=g), g)
     assert rep["ok"], rep
-    assert abs(rep["mean_cos"] - G) < 0.02
+    assert abs(rep["mean_cos"] - g) < 0.02
 
 
 @pytest.mark.parametrize("mutant,kind", [(1, "nee"), (2, "sampling"), (3, "nee"), (4, "nee")])
@@ -248,16 +266,19 @@ GPU_SHAPE = (64, 64, 16, 64)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["plain", "runs", "temperature"])
-def test_gpu_single_scatter_matches_analytic(variant):
+@pytest.mark.parametrize("variant,g",
+                         [("plain", G), ("runs", G), ("temperature", G)] + [("plain", g) for g in SCATTER_G[1:]],
+                         ids=["plain", "runs", "temperature"] + [f"plain-g={g:g}" for g in SCATTER_G[1:]])
+def test_gpu_single_scatter_matches_analytic(variant, g):
     """Production kernels (density-only with and without run skipping, and the temperature kernel with a
-    constant temperature grid: sigma_a = 0 makes its emission 0), 64x64 pixels, 16 batches of 64 waves."""
+    constant temperature grid: sigma_a = 0 makes its emission 0), 64x64 pixels, 16 batches of 64 waves; the
+    plain kernel also at the other g of SCATTER_G."""
     import torch
 
     from volume_path_tracer_amd.render import Integrator
 
     w, h, K, spp_b = GPU_SHAPE
-    wl = scatter_config(w, h, K * spp_b)
+    wl = scatter_config(w, h, K * spp_b, g)
     temp = SynthGrid(0, 128).grid() if variant == "temperature" else None
     it = Integrator(wl.cfg, SynthGrid(0, 128).grid(), temp, device=0)
     if variant != "temperature":
@@ -268,22 +289,23 @@ def test_gpu_single_scatter_matches_analytic(variant):
         it.render_waves(1 + k * spp_b, spp_b, film=films[k])
     torch.cuda.synchronize()
     rep = scatter_report(wl.cfg, films.cpu().numpy())
-    print(variant, rep)
+    print(variant, g, rep)
     assert rep["ok"], rep
     assert rep["pixels"] >= 2000
 
 
 @pytest.mark.gpu
-def test_gpu_hg_sampling_law():
+@pytest.mark.parametrize("g", SAMPLING_G)
+def test_gpu_hg_sampling_law(g):
     """Scatter directions of the HIP integrator's event log (the Logger variant of the kernel, which runs
     the production kernel's device code with the event sink on)."""
     from volume_path_tracer_amd.render import Integrator
 
-    wl = sampling_config(32, 32, 4)
+    wl = sampling_config(32, 32, 4, g)
     it = Integrator(wl.cfg, SynthGrid(0, 128).grid(), None, device=0)
     ev = it.trace_jobs(0, wl.cfg.jobs_per_wave() * wl.spp, capacity=1 << 23)
-    rep = sampling_report(ev, G)
-    print(rep)
+    rep = sampling_report(ev, g)
+    print(g, rep)
     assert rep["ok"], rep
     assert rep["scatters"] >= 20000
-    assert abs(rep["mean_cos"] - G) < 0.01
+    assert abs(rep["mean_cos"] - g) < 0.01
