@@ -395,6 +395,43 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
                                   uint32_t* waves_T_host, float* err_T_host, vpt_adaptive_result* out,
                                   void* hip_stream);
 
+/* Alpha (coverage).  One deterministic pass that says how much of each pixel the medium covers: no random numbers,
+ * no noise, a small fraction of a frame's cost.  Asynchronous on `hip_stream`; reads the scene and the density grid
+ * only (never a film, a moment plane or the temperature grid) and writes the caller's planes.
+ *
+ * Definition.  Under delta tracking a primary ray has no real collision with probability exp(-tau),
+ *     tau = sigma_t * integral of rho ds over the ray's positive-majorant segments
+ * (RayMajorantIterator's segments inside Volume::intersect's clip; a segment whose majorant is <= 0 draws nothing
+ * and counts nothing; rho is the trilinear density the integrator evaluates).  The pass walks the integrator's own
+ * clip and segments, cuts every positive segment where the ray crosses an integer lattice plane of index space --
+ * the field is a cubic of t between two crossings -- and adds Simpson's rule per piece,
+ *     (tb - ta) * ((rho(ta) + 4 rho(tm)) + rho(tb)),  tm = ta + 0.5 (tb - ta),
+ * pieces into their segment's sum, segment sums into the ray's, tau = (sigma_t * m_scale) * (sum / 6) clamped at
+ * >= 0.  All fp32, not contracted, divisions and square roots correctly rounded, crossing times computed from
+ * their integer plane as (k - e) * invDir (never accumulated): the tau plane is a function of the scene alone and
+ * equals the host build of the same code (csrc/vpt_alpha.h) bit for bit.  A ray that misses the clip has tau = +0.
+ *
+ * Footprint.  `sub` in 1..8 sub-rays per axis.  The reference jitters a pixel's raster point over
+ * [px + 0.5, px + 1) x [py + 0.5, py + 1) (jitter scale 0.5, worker.cpp:122); the matte averages that footprint.
+ * Sub-ray (i, j), i, j in [0, sub), has the raster point
+ *     ((float)px + 0.5f) + jitter_scale * (((float)i + 0.5f) / (float)sub),   likewise y with j,
+ * and the camera ray Camera::generate_ray forms from it (the integrator's expressions and order).  With use_jitter
+ * off all sub-rays coincide and one is evaluated (n = 1; otherwise n = sub * sub).
+ *
+ * Outputs, device float[H][W], caller-owned.  With the sub-rays taken in row-major order (j outer, i inner):
+ *     alpha = 1 - (sum_k expf(-tau_k)) / n          tau = (sum_k tau_k) / n   (tau_device may be NULL)
+ * both sums in that fixed order.  For n == 1 the tau plane is the ray's optical depth.  Every pixel of the frame is
+ * written, so the caller need not clear; in single-pixel mode only that pixel is.  Rays that miss store +0.0.
+ * The alpha plane depends on the platform's expf: within 2^-22 of 1 - exp(-tau) for n == 1.
+ *
+ * Launch: one wavefront per (tile, chunk of 64 pixels), tiles by descending cost (vpt_gpu_tile_costs' ranks, which
+ * the context computes once, at the first call that needs them; nothing else is allocated).
+ * VPT_E_INVALID: a null context or alpha plane, sub outside 1..8.  VPT_E_STATE while a feed of the context is
+ * launched and not closed (the tile-list launch's rule: the pass must not queue behind a launch that holds the
+ * device).  Out of scope: the drop-in vpt_gpu::run (the reference's film has no alpha), the multi-GPU modes,
+ * per-band alpha, depth and other AOVs. */
+int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, float* tau_device, void* hip_stream);
+
 /* The drop-in's ordered frame (vpt_run.hpp: vpt_gpu::run's film, bit-identical to the reference's).  A feed's jobs
  * arrive in the provider's order and its film is progressive, so its launch adds samples with fp32 atomics; with a
  * frame open, the context's feed launches also store the samples of the jobs of tiles [tile_lo, tile_hi) in waves

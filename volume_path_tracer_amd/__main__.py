@@ -9,8 +9,11 @@ reference's volumes are not shipped).  ``--spp`` overrides num_waves; ``--size W
 output_size.  ``--adaptive ERR`` renders until every tile's error estimate is at most ERR
 (render.render_adaptive): ``--spp`` becomes the cap, ``--min-spp`` / ``--spp-step`` the first round and
 the later rounds' waves, ``--waves-out`` saves the per-tile wave map, ``--adaptive-fused`` runs the
-one-launch driver (the same bytes).  Exits 1 on a fatal error, like
-vptFATAL.
+one-launch driver (the same bytes).  ``--alpha`` writes an RGBA PNG: the same RGB bytes plus the coverage
+matte (Integrator.render_alpha) as A = round(255 * alpha); ``--alpha-foreground`` (implies ``--alpha``) first
+removes the environment light seen through the medium (image.foreground_film; straight alpha);
+``--alpha-sub N`` sets the matte's sub-rays per axis, ``--alpha-out`` saves the alpha plane (.npy).  Exits 1 on a
+fatal error, like vptFATAL.
 """
 from __future__ import annotations
 
@@ -48,6 +51,12 @@ def main(argv=None) -> int:
     ap.add_argument("--adaptive-fused", action="store_true",
                     help="adaptive: the one-launch driver (vpt_gpu_render_adaptive_fused; tiles of at most 256 pixels)")
     ap.add_argument("--waves-out", default=None, help="adaptive: save the per-tile wave map (.npy, uint32[T])")
+    ap.add_argument("--alpha", action="store_true", help="write an RGBA PNG: A = round(255 * coverage)")
+    ap.add_argument("--alpha-foreground", action="store_true",
+                    help="implies --alpha: RGB of the medium alone (environment light removed), straight alpha")
+    ap.add_argument("--alpha-sub", type=int, default=None, metavar="N",
+                    help="alpha: N x N sub-rays per pixel, 1..8 (default 4 with jitter, 1 without)")
+    ap.add_argument("--alpha-out", default=None, help="alpha: save the alpha plane (.npy, float32 [H][W])")
     args = ap.parse_args(argv)
 
     from . import image, traces, volumes
@@ -106,7 +115,18 @@ def main(argv=None) -> int:
             import numpy as np
 
             np.save(args.film_out, film)
-        image.save_png(args.output_path, image.film_to_image(film))
+        if args.alpha or args.alpha_foreground or args.alpha_out:
+            import numpy as np
+
+            alpha = it.render_alpha(sub=args.alpha_sub)
+            if args.alpha_out:
+                np.save(args.alpha_out, alpha)
+        if args.alpha or args.alpha_foreground:
+            rgb = image.film_to_image(image.foreground_film(film, alpha, cfg) if args.alpha_foreground else film)
+            a8 = np.rint(np.float32(255.0) * alpha).astype(np.uint8)
+            image.save_png(args.output_path, np.concatenate([rgb, a8[..., None]], axis=2))
+        else:
+            image.save_png(args.output_path, image.film_to_image(film))
     except Exception as e:  # vptFATAL: message and exit(1)
         print(f"[vpt] FATAL: {e}", file=sys.stderr)
         return 1

@@ -264,6 +264,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "vpt_gpu_render_adaptive_fused"):
         L.vpt_gpu_render_adaptive_fused.argtypes = [vp, C.POINTER(AdaptiveParams), vp, vp, C.POINTER(C.c_uint32), fp,
                                                     C.POINTER(AdaptiveResult), vp]
+    if hasattr(L, "vpt_gpu_render_alpha"):  # (older builds in A/B runs lack the coverage pass)
+        L.vpt_gpu_render_alpha.argtypes = [vp, C.c_uint32, vp, vp, vp]
     L.vpt_gpu_sync.argtypes = [vp]
     L.vpt_gpu_film_clear.argtypes = [vp]
     L.vpt_gpu_film_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]

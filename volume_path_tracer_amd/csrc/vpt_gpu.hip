@@ -1000,6 +1000,29 @@ int vpt_gpu_render_tile_list(vpt_gpu_ctx* ctx, const uint32_t* tiles, uint32_t n
   return render_band_waves(ctx, 0, n, true, wave_begin, wave_count, film_device, hip_stream);
 }
 
+int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, float* tau_device, void* hip_stream) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: null context");
+  if (!alpha_device) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: null alpha plane");
+  if (sub < 1 || sub > vpt::kAlphaMaxSub)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: sub-rays per axis must be 1..8");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_alpha: a feed of this context is open");
+  if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
+  const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
+  if (blocks >= (1ULL << 31)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: 2^31 or more pixel chunks");
+  hipStream_t s = (hipStream_t)hip_stream;
+  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the pass as for any launch)
+  if ((rc = take_slot(ctx, s, slot))) return rc;
+  hipLaunchKernelGGL(vpt::vpt_alpha_kernel, dim3((unsigned)blocks), dim3(64), 0, s, ctx->scene_dev,
+                     (const uint32_t*)ctx->order, sub, alpha_device, tau_device);
+  const hipError_t e = hipGetLastError();
+  if ((rc = release_slot(ctx, s, slot))) return rc;
+  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_render_alpha: ") + hipGetErrorString(e));
+  return VPT_OK;
+}
+
 int vpt_gpu_set_film_moments(vpt_gpu_ctx* ctx, float* m2_device) {
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_film_moments: null context");
   if (m2_device && ctx->film_order != VPT_FILM_ORDERED)

@@ -1,11 +1,12 @@
 // vpt_kernels.h — the integrator's device code: the launch arguments, the kernel environment (cold lane
 // state in LDS or VGPRs, the feed protocol's fetch, the regrouped film adds / ordered-film stores), live-path
-// compaction, and the kernels (integrator, film passes, seed search, majorant trace, tile costs).  Included by
+// compaction, and the kernels (integrator, film passes, seed search, majorant trace, tile costs, coverage).  Included by
 // vpt_gpu.hip only (the translation unit that launches them).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "vpt_alpha.h"
 #include "vpt_internal.h"
 #include "vpt_launch.h"
 
@@ -1252,6 +1253,32 @@ __global__ void vpt_tile_cost_kernel(const DevScene* scene, float* cost) {
     c += (float)steps + 4.0f * tau;
   }
   cost[tile] = c;
+}
+
+// The coverage pass (vpt_gpu_render_alpha): alpha = 1 - mean exp(-tau) over each pixel's sub-rays, tau by the
+// deterministic march of vpt_alpha.h.  A block is one wavefront that owns up to 64 pixels of one tile, indexed as
+// vpt_band_order_kernel indexes them -- block = (tile slot, chunk of 64 pixels), lane p = pixel p of the chunk -- so
+// a wavefront's 64 rays walk the same cells and read the same stencils.  Tile slot b renders tile rank[b], the
+// context's descending-cost order: the long rays start first and the short ones fill the tail.  Lanes beyond a
+// ragged tile's pixels, and in single-pixel mode every lane but that pixel's, end at once.  No LDS, no atomics,
+// nothing shared between blocks; every pixel of the frame is written exactly once.
+__global__ __launch_bounds__(64) void vpt_alpha_kernel(const DevScene* scene, const uint32_t* rank, uint32_t sub,
+                                                       float* alpha, float* tau) {
+  const DevScene& S = *scene;
+  const uint32_t area = S.tile_area, chunks = (area + 63u) / 64u;
+  const uint32_t tb = blockIdx.x / chunks, q = (blockIdx.x - tb * chunks) * 64u + threadIdx.x;
+  if ((uint64_t)tb >= S.T) return;
+  const uint32_t t = rank[tb];
+  const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
+  const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
+  if (q >= area || (int32_t)q >= rw * rh) return;
+  const int32_t yl = (int32_t)q / rw, px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
+  if (S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) return;
+  float a, od;
+  alpha_pixel(S, px, py, sub, a, od);
+  const uint64_t p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
+  alpha[p] = a;
+  if (tau) tau[p] = od;
 }
 
 }  // namespace vpt

@@ -30,20 +30,46 @@ def film_to_image(film: np.ndarray) -> np.ndarray:
     return out
 
 
+def foreground_film(film: np.ndarray, alpha: np.ndarray, cfg) -> np.ndarray:
+    """The film of the medium alone: removes the environment light seen through it.  A path that leaves the volume
+    unhit carries exactly the environment light (plus emission picked up at null collisions), so with the matte
+    `alpha` (Integrator.render_alpha) the film is w * imaging_ratio * ((1 - alpha) * Le + alpha * C) and
+
+        xyz' = max(film.xyz - (1 - alpha) * w * imaging_ratio * infinite_light_xyz * multiplier, 0) / alpha
+
+    where alpha > 1/255 (a matte that rounds to at least one 8-bit step), else 0; w is kept.  float32 throughout.
+    The result goes through film_to_image as any film; pair it with the alpha plane as straight alpha."""
+    film = np.asarray(film, dtype=np.float32)
+    alpha = np.asarray(alpha, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 4 or alpha.shape != film.shape[:2]:
+        raise ValueError(f"foreground_film wants film [H][W][4] and alpha [H][W], got {film.shape} and {alpha.shape}")
+    wp = cfg.worker_parameters
+    le = np.asarray(wp.infinite_light_xyz[:], np.float32) * np.float32(wp.infinite_light_multiplier)
+    r = np.float32(cfg.camera_parameters.imaging_ratio)
+    env = ((np.float32(1) - alpha) * film[..., 3] * r)[..., None] * le
+    out = film.copy()
+    cover = alpha > np.float32(1.0 / 255.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fg = np.maximum(film[..., :3] - env, np.float32(0)) / alpha[..., None]
+    out[..., :3] = np.where(cover[..., None], fg, np.float32(0))
+    return out
+
+
 def _chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
 def encode_png(rgb: np.ndarray) -> bytes:
-    """uint8 [H][W][3] (or uint16) -> PNG bytes (truecolor, filter 0 per row)."""
+    """uint8 [H][W][3] (or uint16) -> PNG bytes (truecolor, filter 0 per row); [H][W][4] -> truecolor with
+    (straight) alpha, colour type 6."""
     rgb = np.ascontiguousarray(rgb)
-    if rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.dtype not in (np.uint8, np.uint16):
-        raise ValueError("encode_png wants uint8/uint16 [H][W][3]")
+    if rgb.ndim != 3 or rgb.shape[2] not in (3, 4) or rgb.dtype not in (np.uint8, np.uint16):
+        raise ValueError("encode_png wants uint8/uint16 [H][W][3] or [H][W][4]")
     h, w = rgb.shape[:2]
     depth = 8 * rgb.dtype.itemsize
     rows = rgb.astype(rgb.dtype.newbyteorder(">"), copy=False).reshape(h, -1).view(np.uint8)
     raw = np.concatenate([np.zeros((h, 1), np.uint8), rows], axis=1).tobytes()
-    ihdr = struct.pack(">IIBBBBB", w, h, depth, 2, 0, 0, 0)
+    ihdr = struct.pack(">IIBBBBB", w, h, depth, 2 if rgb.shape[2] == 3 else 6, 0, 0, 0)
     return (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(raw, 6))
             + _chunk(b"IEND", b""))
 
@@ -53,7 +79,8 @@ def save_png(path, rgb: np.ndarray) -> None:
 
 
 def decode_png(data: bytes) -> np.ndarray:
-    """Minimal reader for truecolor 8/16-bit non-interlaced PNGs (tests and tools)."""
+    """Minimal reader for truecolor 8/16-bit non-interlaced PNGs, with or without alpha (tests and tools):
+    [H][W][3] for colour type 2, [H][W][4] for colour type 6."""
     if data[:8] != b"\x89PNG\r\n\x1a\n":
         raise ValueError("not a PNG")
     pos, idat, hdr = 8, [], None
@@ -66,9 +93,10 @@ def decode_png(data: bytes) -> np.ndarray:
             idat.append(body)
         pos += 12 + n
     w, h, depth, ctype, _, _, interlace = hdr
-    if ctype != 2 or interlace != 0 or depth not in (8, 16):
+    if ctype not in (2, 6) or interlace != 0 or depth not in (8, 16):
         raise ValueError("decode_png supports truecolor 8/16-bit non-interlaced only")
-    bpp = 3 * depth // 8
+    ch = 3 if ctype == 2 else 4
+    bpp = ch * depth // 8
     raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(h, 1 + w * bpp)
     if not raw[:, 0].any():  # every row unfiltered (what encode_png writes)
         out = raw[:, 1:].astype(np.int32)
@@ -76,8 +104,8 @@ def decode_png(data: bytes) -> np.ndarray:
         out = _unfilter(raw, h, w * bpp, bpp)
     img = out.astype(np.uint8)
     if depth == 16:
-        return img.reshape(h, w * 3, 2).view(">u2").reshape(h, w, 3).astype(np.uint16)
-    return img.reshape(h, w, 3)
+        return img.reshape(h, w * ch, 2).view(">u2").reshape(h, w, ch).astype(np.uint16)
+    return img.reshape(h, w, ch)
 
 
 def _unfilter(raw, h, stride, bpp):

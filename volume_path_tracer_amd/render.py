@@ -243,6 +243,28 @@ class Integrator:
                                                   C.c_void_p(self.stream_handle(stream))), "vpt_gpu_tile_errors")
         return err
 
+    def render_alpha(self, sub=None, tau: bool = False, stream=None):
+        """The coverage matte, numpy float32 [H][W]: alpha = 1 - mean exp(-optical depth) over sub x sub sub-rays of
+        each pixel's jitter footprint, by one deterministic pass (vpt_gpu_render_alpha: no random numbers, no
+        noise).  sub=None: 4 with jitter, 1 without (all sub-rays coincide then).  tau=True: (alpha, tau) with the
+        mean optical depth plane.  Synchronous (the planes are read back); in single-pixel mode every other pixel
+        is 0.  Touches no film."""
+        torch = self.torch
+        if sub is None:
+            sub = 4 if self.cfg.worker_parameters.use_jitter else 1
+        if not 1 <= int(sub) <= 8:
+            raise ValueError("render_alpha: sub is 1..8 sub-rays per axis")
+        shape = (self.cfg.height, self.cfg.width)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        with torch.cuda.stream(s):  # (the zero fills run on the pass's stream, ahead of it)
+            a = torch.zeros(shape, dtype=torch.float32, device=self.dev)
+            t = torch.zeros(shape, dtype=torch.float32, device=self.dev) if tau else None
+        capi.check(capi.lib().vpt_gpu_render_alpha(self.h, int(sub), C.c_void_p(a.data_ptr()),
+                                                   C.c_void_p(t.data_ptr()) if tau else None,
+                                                   C.c_void_p(int(s.cuda_stream))), "vpt_gpu_render_alpha")
+        s.synchronize()
+        return (a.cpu().numpy(), t.cpu().numpy()) if tau else a.cpu().numpy()
+
     def trace_jobs(self, jid_begin: int, jid_count: int, capacity: int = 1 << 20, film=None, stream=None):
         """Render jobs and return their Logger events (worker.cpp:16-48) as a numpy array of
         capi.EVENT_DTYPE sorted by (jid, seq).  Raises if more than `capacity` events occur."""
