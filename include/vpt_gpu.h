@@ -432,6 +432,62 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
  * per-band alpha, depth and other AOVs. */
 int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, float* tau_device, void* hip_stream);
 
+/* Denoise.  A variance-guided a-trous filter over a film and its moment plane, optionally guided by up to four
+ * feature planes (the matte's alpha and tau / (1 + tau) are the ones a volume has).  The film is not changed: the
+ * denoised film is a second output, an ordinary film (XYZ sums and the count n) that every film consumer takes.
+ * Asynchronous on `hip_stream`; takes a launch slot, so vpt_gpu_sync covers it; reads film, plane and guides only;
+ * works on any film with a matching plane (uniform, band, tile-list, either adaptive driver: tiles may hold different
+ * wave counts); independent of the scene and of the RNG mode.
+ *
+ * Arithmetic (fp32, not contracted, only + - * /, sqrtf, fabsf and comparisons, divisions and square roots
+ * correctly rounded, in exactly this order: csrc/vpt_denoise.h is the code, tests/denoise_ref.py its numpy
+ * restatement, and the device, the host build and numpy give the same bytes).
+ *   Prepare, per pixel.  Valid iff n >= 1 (film.w; NaN is invalid).  c = xyz / n.  n >= 2:
+ *     v = max(m2 / n - c.y c.y, 0) / (n - 1)   (the square of vpt_gpu_tile_errors' se, its expression order);
+ *   otherwise v = c.y c.y.  An invalid pixel is never a tap (a select, so NaN or garbage in an unrendered pixel
+ *   cannot leak) and its output is its input, copied.
+ *   Iteration i = 0 .. iterations - 1, step s = 2^i, per valid pixel p:
+ *     gv  = (sum b v_q) / (sum b) over the valid in-image neighbours q = p + (dx, dy), dy, dx in -1..1 (dy outer),
+ *           b = b3[dy] * b3[dx], b3 = {1/4, 1/2, 1/4}, both sums sequential;
+ *     den = (sigma_l * sqrtf(gv) + rel_floor * c_p.y) + 1e-20f;
+ *     for q = p + s (dx, dy), dy, dx in -2..2 (dy outer), in the image and valid:
+ *       d = fabsf(c_p.y - c_q.y) / den;   w = (h[dy] * h[dx]) / (1 + d d),   h = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *       for k = 0 .. n_guides - 1:  e = (g_k[p] - g_k[q]) / guide_sigma[k];  w = w / (1 + e e);
+ *       acc += w c_q;   accv += (w w) v_q;   ws += w;        (sequential; the centre tap always counts: ws > 0)
+ *     c_p' = acc / ws;   v_p' = accv / (ws ws).
+ *   Iterations ping-pong between two packed planes; none reads what it writes.
+ *   Finish.  out.xyz = c n, out.w = n.  var_out (may be NULL) receives the final v, the filtered variance of the
+ *   mean of Y (a confidence map); +0 at an invalid pixel.
+ *
+ * Kernels: vpt_denoise_prepare_kernel packs (c, v) and the guides into float4 planes (an invalid pixel has v = -1),
+ * vpt_denoise_atrous_kernel<G> runs once per iteration in blocks of 64 x 4 pixels -- a wavefront owns 64
+ * consecutive pixels of a row, so every tap is one 16-byte load per lane -- and the last iteration stores the
+ * finished film.  Scratch: 32 bytes per pixel, 48 with guides; it belongs to the context, is allocated by the
+ * first call, grown when a later call needs more and freed by vpt_gpu_destroy.  Every call of a context uses the
+ * same planes, so calls are serialised on the device: a call's kernels wait, on its own stream, for the previous
+ * call's last iteration whatever stream that ran on (an event, as for the ordered film's sample buffer), and calls
+ * from several threads take a lock around their launches.  Calls on different streams are therefore safe and run
+ * one after the other; the caller's film, plane and guides must be ready on `hip_stream`.
+ * Alignment: film_device and out_film_device are read and written 16 bytes at a time and must be 16-byte aligned
+ * (any device allocation is); the planes and guides must be 4-byte aligned.
+ *
+ * VPT_E_INVALID: a null context, params, film, plane or output film; iterations outside 1..6; n_guides > 4 or a null
+ * guide; sigma_l, rel_floor or a used guide_sigma that is not > 0 (NaN included); a film that is not 16-byte or a
+ * plane that is not 4-byte aligned; an output that overlaps an input or the other output.  VPT_E_STATE while a feed of the context is launched and not closed (the tile-list launch's
+ * rule: the call allocates and must not queue behind a launch that holds the device).  Out of scope: the drop-in
+ * vpt_gpu::run and feeds (no moment plane there), the multi-GPU modes, temporal filtering, colour-channel
+ * variances (only Y has a moment), learned denoisers. */
+typedef struct vpt_denoise_params {
+  uint32_t iterations; /* 1..6; 4 is a good default */
+  uint32_t n_guides;   /* 0..4 */
+  float sigma_l;       /* Y distance scale in local standard deviations; default 4 */
+  float rel_floor;     /* relative floor of that scale; default 1e-3 */
+  float guide_sigma[4];
+} vpt_denoise_params;
+int vpt_gpu_denoise(vpt_gpu_ctx* ctx, const vpt_denoise_params* p, const float* film_device, const float* m2_device,
+                    const float* const* guides_device /* n_guides device planes float[H][W]; may be NULL when 0 */,
+                    float* out_film_device, float* var_out_device /* may be NULL */, void* hip_stream);
+
 /* The drop-in's ordered frame (vpt_run.hpp: vpt_gpu::run's film, bit-identical to the reference's).  A feed's jobs
  * arrive in the provider's order and its film is progressive, so its launch adds samples with fp32 atomics; with a
  * frame open, the context's feed launches also store the samples of the jobs of tiles [tile_lo, tile_hi) in waves

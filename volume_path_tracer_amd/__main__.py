@@ -12,8 +12,15 @@ the later rounds' waves, ``--waves-out`` saves the per-tile wave map, ``--adapti
 one-launch driver (the same bytes).  ``--alpha`` writes an RGBA PNG: the same RGB bytes plus the coverage
 matte (Integrator.render_alpha) as A = round(255 * alpha); ``--alpha-foreground`` (implies ``--alpha``) first
 removes the environment light seen through the medium (image.foreground_film; straight alpha);
-``--alpha-sub N`` sets the matte's sub-rays per axis, ``--alpha-out`` saves the alpha plane (.npy).  Exits 1 on a
-fatal error, like vptFATAL.
+``--alpha-sub N`` sets the matte's sub-rays per axis, ``--alpha-out`` saves the alpha plane (.npy).
+``--denoise`` writes the PNG from the denoised film (Integrator.denoise: the variance-guided a-trous filter over the
+film and its moment plane, guided by the matte's alpha and tau / (1 + tau) unless ``--denoise-no-guides``): the
+uniform frame is then rendered as one ordered launch with a moment plane (render.render_uniform: the reference's film
+bit for bit) instead of through the feed, the guides come from one coverage pass with ``--alpha-sub`` (default 1)
+sub-rays, which also serves ``--alpha``, and ``--alpha-foreground`` applies to the denoised film.
+``--denoise-iters N`` and ``--denoise-sigma S`` set the iterations (1..6, default 4) and the Y scale (default 4);
+``--denoised-film-out`` and ``--moments-out`` save the denoised film and the moment plane (.npy); ``--film-out``
+still saves the raw film.  Exits 1 on a fatal error, like vptFATAL.
 """
 from __future__ import annotations
 
@@ -57,10 +64,19 @@ def main(argv=None) -> int:
     ap.add_argument("--alpha-sub", type=int, default=None, metavar="N",
                     help="alpha: N x N sub-rays per pixel, 1..8 (default 4 with jitter, 1 without)")
     ap.add_argument("--alpha-out", default=None, help="alpha: save the alpha plane (.npy, float32 [H][W])")
+    ap.add_argument("--denoise", action="store_true", help="write the PNG from the denoised film (Integrator.denoise)")
+    ap.add_argument("--denoise-iters", type=int, default=4, metavar="N", help="denoise: a-trous iterations, 1..6")
+    ap.add_argument("--denoise-sigma", type=float, default=4.0, metavar="S",
+                    help="denoise: Y distance scale in local standard deviations (sigma_l)")
+    ap.add_argument("--denoise-no-guides", action="store_true", help="denoise: do not guide by the matte's planes")
+    ap.add_argument("--denoised-film-out", default=None, help="denoise: save the denoised XYZW film (.npy)")
+    ap.add_argument("--moments-out", default=None, help="denoise: save the film's moment plane (.npy, float32 [H][W])")
     args = ap.parse_args(argv)
+    if (args.denoised_film_out or args.moments_out) and not args.denoise:
+        ap.error("--denoised-film-out and --moments-out need --denoise")
 
     from . import image, traces, volumes
-    from .render import Integrator, TileProvider, render_adaptive, run
+    from .render import Integrator, TileProvider, matte_guides, render_adaptive, render_uniform, run
     from .scenes import SynthGrid, read_configuration
 
     try:
@@ -86,10 +102,12 @@ def main(argv=None) -> int:
 
         it = Integrator(cfg, dens, temp, device=args.device)
         t0 = time.perf_counter()
+        m2 = None
         if args.adaptive is not None:
-            film, waves, err, info = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
-                                                     step_waves=args.spp_step, max_waves=cfg.num_waves,
-                                                     fused=args.adaptive_fused)
+            film, waves, err, info, *plane = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
+                                                             step_waves=args.spp_step, max_waves=cfg.num_waves,
+                                                             fused=args.adaptive_fused, return_moments=args.denoise)
+            m2 = plane[0] if plane else None
             ms = (time.perf_counter() - t0) * 1e3
             driver = "one launch (fused)" if args.adaptive_fused else "rounds"
             print(f"[vpt] Adaptive rendering ({driver} driver) complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, "
@@ -101,6 +119,11 @@ def main(argv=None) -> int:
                 import numpy as np
 
                 np.save(args.waves_out, waves)
+        elif args.denoise:  # the ordered frame with its moment plane (the feed keeps none)
+            film, m2 = (t.cpu().numpy() for t in render_uniform(it))
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
+                  file=sys.stderr)
         else:
             tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
             tp.reset_eta()
@@ -118,9 +141,29 @@ def main(argv=None) -> int:
         if args.alpha or args.alpha_foreground or args.alpha_out:
             import numpy as np
 
-            alpha = it.render_alpha(sub=args.alpha_sub)
+            if args.denoise and not args.denoise_no_guides:  # one pass serves the matte and the guides
+                guides = matte_guides(it, sub=args.alpha_sub or 1)
+                alpha = guides[0]
+            else:
+                alpha = it.render_alpha(sub=args.alpha_sub)
             if args.alpha_out:
                 np.save(args.alpha_out, alpha)
+        if args.denoise:
+            import numpy as np
+
+            if args.denoise_no_guides:
+                guides = []
+            elif not (args.alpha or args.alpha_foreground or args.alpha_out):
+                guides = matte_guides(it, sub=args.alpha_sub or 1)
+            if args.moments_out:
+                np.save(args.moments_out, m2)
+            t1 = time.perf_counter()
+            film = it.denoise(film, m2, guides, iterations=args.denoise_iters, sigma_l=args.denoise_sigma)
+            ms = (time.perf_counter() - t1) * 1e3
+            print(f"[vpt] Denoised in {ms:.1f} ms ({args.denoise_iters} iterations, {len(guides)} guides, "
+                  f"sigma {args.denoise_sigma:g})", file=sys.stderr)
+            if args.denoised_film_out:
+                np.save(args.denoised_film_out, film)
         if args.alpha or args.alpha_foreground:
             rgb = image.film_to_image(image.foreground_film(film, alpha, cfg) if args.alpha_foreground else film)
             a8 = np.rint(np.float32(255.0) * alpha).astype(np.uint8)

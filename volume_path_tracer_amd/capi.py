@@ -103,6 +103,27 @@ class AdaptiveResult(C.Structure):
         return {n: (float if n == "max_error" else int)(getattr(self, n)) for n, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    """vpt_denoise_params (vpt_gpu_denoise)."""
+    _fields_ = [("iterations", C.c_uint32), ("n_guides", C.c_uint32), ("sigma_l", C.c_float), ("rel_floor", C.c_float),
+                ("guide_sigma", C.c_float * 4)]
+
+    @classmethod
+    def make(cls, iterations=4, n_guides=0, sigma_l=4.0, rel_floor=1e-3, guide_sigma=None):
+        """guide_sigma None: 0.2 per guide; a number: that for every guide; else one per guide."""
+        if guide_sigma is None:
+            guide_sigma = 0.2
+        if np.isscalar(guide_sigma):
+            guide_sigma = [guide_sigma] * n_guides
+        gs = [float(v) for v in guide_sigma][:4]
+        if len(gs) < min(n_guides, 4):
+            raise ValueError("denoise: one guide_sigma per guide")
+        gs += [1.0] * (4 - len(gs))
+        return cls(int(iterations), int(n_guides), float(sigma_l), float(rel_floor), (C.c_float * 4)(*gs))
+
+
+assert C.sizeof(DenoiseParams) == 32
+
 # vpt_event (include/vpt_gpu.h): one Logger line (src/worker.cpp:16-48)
 EVENT_DTYPE = np.dtype([("jid", "<u8"), ("pixel", "<u4"), ("seq", "<u4"), ("type", "<u4"), ("v", "<f4", (7,))])
 assert EVENT_DTYPE.itemsize == 48
@@ -266,6 +287,8 @@ def lib() -> C.CDLL:
                                                     C.POINTER(AdaptiveResult), vp]
     if hasattr(L, "vpt_gpu_render_alpha"):  # (older builds in A/B runs lack the coverage pass)
         L.vpt_gpu_render_alpha.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    if hasattr(L, "vpt_gpu_denoise"):  # (older builds in A/B runs lack the denoiser)
+        L.vpt_gpu_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, C.POINTER(vp), vp, vp, vp]
     L.vpt_gpu_sync.argtypes = [vp]
     L.vpt_gpu_film_clear.argtypes = [vp]
     L.vpt_gpu_film_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]

@@ -168,6 +168,16 @@ struct vpt_gpu_ctx {
   float* gang_scratch = nullptr;
   uint64_t gang_scratch_bytes = 0;
   uint32_t* gang_waves = nullptr;
+  // The denoiser's packed planes (vpt_gpu_denoise): two float4 [H][W] planes, a third with guides.  Allocated by the
+  // first call, grown when a call needs more, freed with the context.
+  // The planes are shared by every call, on whatever stream: a call's kernels wait for the previous call's
+  // (denoise_done, recorded after the last iteration; as samples_done serialises the ordered launches), and
+  // denoise_mu makes sizing, wait, launches and record one step for calls from several threads.
+  void* denoise_scratch = nullptr;
+  uint64_t denoise_scratch_bytes = 0;
+  hipEvent_t denoise_done = nullptr;
+  bool denoise_used = false;
+  std::mutex denoise_mu;
   // The drop-in's ordered frame (vpt_gpu_frame_open / _finish): its feed launches also store the samples of the
   // frame's tiles [frame_tile_lo, + frame_tiles) from job frame_jid_lo on into the sample buffer above, frame_waves
   // waves of those tiles (0: no frame open); the order pass writes frame_film (device, film_count floats), copied

@@ -29,6 +29,7 @@
 
 #include "vpt_ctx.h"
 #include "vpt_kernels.h"
+#include "vpt_denoise.h"
 
 namespace vpt {
 
@@ -193,10 +194,12 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->tile_err);
   (void)hipFree(ctx->gang_scratch);
   (void)hipFree(ctx->gang_waves);
+  (void)hipFree(ctx->denoise_scratch);
   (void)hipFree(ctx->perm);
   (void)hipFree(ctx->samples);
   (void)hipFree(ctx->frame_film);
   if (ctx->samples_done) (void)hipEventDestroy(ctx->samples_done);
+  if (ctx->denoise_done) (void)hipEventDestroy(ctx->denoise_done);
   for (uint32_t i = 0; i < kLaunchSlots; ++i)
     if (ctx->slot_done[i]) (void)hipEventDestroy(ctx->slot_done[i]);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -850,6 +853,24 @@ int render_band_waves(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t B, bool list,
   }
   return VPT_OK;
 }
+
+// vpt_gpu_denoise: byte ranges that share an address; one iteration's launch.
+bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && a0 < b0 + bn && b0 < a0 + an;
+}
+
+template <int G>
+void launch_denoise_atrous(bool last, dim3 grid, dim3 block, hipStream_t s, const vpt::DenoiseArgs& A, int32_t step,
+                           const float4* src, const float4* gd, float4* dst, const float4* film, float4* out_film,
+                           float* var_out) {
+  if (last)
+    hipLaunchKernelGGL((vpt::vpt_denoise_atrous_kernel<G, true>), grid, block, 0, s, A, step, src, gd, dst, film, out_film,
+                       var_out);
+  else
+    hipLaunchKernelGGL((vpt::vpt_denoise_atrous_kernel<G, false>), grid, block, 0, s, A, step, src, gd, dst, film, out_film,
+                       var_out);
+}
 }  // namespace
 
 extern "C" {
@@ -1020,6 +1041,107 @@ int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, fl
   const hipError_t e = hipGetLastError();
   if ((rc = release_slot(ctx, s, slot))) return rc;
   if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_render_alpha: ") + hipGetErrorString(e));
+  return VPT_OK;
+}
+
+int vpt_gpu_denoise(vpt_gpu_ctx* ctx, const vpt_denoise_params* p, const float* film_device, const float* m2_device,
+                    const float* const* guides_device, float* out_film_device, float* var_out_device, void* hip_stream) {
+  // (the arguments are checked before the context, so that every refusal is testable without a device)
+  if (!p) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: null params");
+  if (!film_device || !m2_device || !out_film_device)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: null film, moment plane or output film");
+  if (p->iterations < 1 || p->iterations > vpt::kDenoiseMaxIterations)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: iterations must be 1..6");
+  if (p->n_guides > vpt::kDenoiseMaxGuides) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: at most 4 guides");
+  if (!(p->sigma_l > 0.0f) || !(p->rel_floor > 0.0f))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: sigma_l and rel_floor must be > 0");
+  if (p->n_guides && !guides_device) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: null guide array");
+  for (uint32_t k = 0; k < p->n_guides; ++k) {
+    if (!guides_device[k]) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: null guide plane");
+    if (!(p->guide_sigma[k] > 0.0f)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: guide_sigma must be > 0");
+  }
+  // (float4 loads and stores on the films; the planes are read and written as floats)
+  bool aligned = ((uintptr_t)film_device | (uintptr_t)out_film_device) % 16 == 0 &&
+                 ((uintptr_t)m2_device | (uintptr_t)var_out_device) % 4 == 0;
+  for (uint32_t k = 0; k < p->n_guides; ++k) aligned = aligned && (uintptr_t)guides_device[k] % 4 == 0;
+  if (!aligned)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: the films must be 16-byte aligned, the planes 4-byte aligned");
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: null context");
+  const size_t N = (size_t)ctx->scene.W * (size_t)ctx->scene.H, fb = N * 4 * sizeof(float), pb = N * sizeof(float);
+  bool alias = ranges_overlap(out_film_device, fb, film_device, fb) || ranges_overlap(out_film_device, fb, m2_device, pb) ||
+               ranges_overlap(out_film_device, fb, var_out_device, pb) ||
+               ranges_overlap(var_out_device, pb, film_device, fb) || ranges_overlap(var_out_device, pb, m2_device, pb);
+  for (uint32_t k = 0; k < p->n_guides; ++k)
+    alias = alias || ranges_overlap(out_film_device, fb, guides_device[k], pb) ||
+            ranges_overlap(var_out_device, pb, guides_device[k], pb);
+  if (alias) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: an output overlaps an input or the other output");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0)  // (the call allocates, and its launches would queue behind the feed's)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_denoise: a feed of this context is open");
+  const uint32_t G = p->n_guides;
+  const uint64_t bytes = (uint64_t)N * sizeof(float4) * (G ? 3u : 2u);
+  // The packed planes are the context's, shared by every call: from here to the record below one call at a time.
+  std::lock_guard<std::mutex> scratch_lock(ctx->denoise_mu);
+  if (!ctx->denoise_done) VPT_HIP(hipEventCreateWithFlags(&ctx->denoise_done, hipEventDisableTiming));
+  if (ctx->denoise_scratch_bytes < bytes) {
+    if (ctx->denoise_used) VPT_HIP(hipEventSynchronize(ctx->denoise_done));  // no earlier call still uses the planes
+    (void)hipFree(ctx->denoise_scratch);
+    ctx->denoise_scratch = nullptr;
+    ctx->denoise_scratch_bytes = 0;
+    const hipError_t e = hipMalloc(&ctx->denoise_scratch, bytes);
+    if (e != hipSuccess) {
+      ctx->denoise_scratch = nullptr;
+      (void)hipGetLastError();
+      return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_denoise: " + std::to_string(bytes >> 20) + " MiB of packed planes: " +
+                                             hipGetErrorString(e));
+    }
+    ctx->denoise_scratch_bytes = bytes;
+  }
+  vpt::DenoiseArgs A{};
+  A.W = ctx->scene.W;
+  A.H = ctx->scene.H;
+  A.sigma_l = p->sigma_l;
+  A.rel_floor = p->rel_floor;
+  vpt::DenoiseGuidePtrs gp{};
+  for (uint32_t k = 0; k < 4; ++k) {
+    A.guide_sigma[k] = k < G ? p->guide_sigma[k] : 1.0f;
+    gp.g[k] = k < G ? guides_device[k] : nullptr;
+  }
+  float4* const plane0 = (float4*)ctx->denoise_scratch;
+  float4* const plane1 = plane0 + N;
+  float4* const gd = G ? plane1 + N : nullptr;
+  const dim3 block(vpt::kDenoiseBlockX, vpt::kDenoiseBlockY);
+  const dim3 grid((unsigned)(((uint64_t)A.W + vpt::kDenoiseBlockX - 1) / vpt::kDenoiseBlockX),
+                  (unsigned)(((uint64_t)A.H + vpt::kDenoiseBlockY - 1) / vpt::kDenoiseBlockY));
+  if (grid.y > 65535u) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_denoise: more than 262140 rows");
+  hipStream_t s = (hipStream_t)hip_stream;
+  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the filter as for any launch)
+  if ((rc = take_slot(ctx, s, slot))) return rc;
+  // The previous call's kernels, on whatever stream they ran, are done with the planes before prepare overwrites them.
+  if (ctx->denoise_used) VPT_HIP(hipStreamWaitEvent(s, ctx->denoise_done, 0));
+  const float4* const film4 = reinterpret_cast<const float4*>(film_device);
+  hipLaunchKernelGGL(vpt::vpt_denoise_prepare_kernel, grid, block, 0, s, A, G, film4, m2_device, gp, plane0, gd);
+  float4 *src = plane0, *dst = plane1;
+  for (uint32_t i = 0; i < p->iterations; ++i) {
+    const bool last = i + 1 == p->iterations;
+    const int32_t step = (int32_t)(1u << i);
+    float4* const of = reinterpret_cast<float4*>(out_film_device);
+    switch (G) {
+      case 0: launch_denoise_atrous<0>(last, grid, block, s, A, step, src, gd, dst, film4, of, var_out_device); break;
+      case 1: launch_denoise_atrous<1>(last, grid, block, s, A, step, src, gd, dst, film4, of, var_out_device); break;
+      case 2: launch_denoise_atrous<2>(last, grid, block, s, A, step, src, gd, dst, film4, of, var_out_device); break;
+      case 3: launch_denoise_atrous<3>(last, grid, block, s, A, step, src, gd, dst, film4, of, var_out_device); break;
+      default: launch_denoise_atrous<4>(last, grid, block, s, A, step, src, gd, dst, film4, of, var_out_device); break;
+    }
+    std::swap(src, dst);
+  }
+  const hipError_t e = hipGetLastError();
+  const hipError_t er = hipEventRecord(ctx->denoise_done, s);  // (recorded whatever was launched: the next call waits)
+  if (er == hipSuccess) ctx->denoise_used = true;
+  if ((rc = release_slot(ctx, s, slot))) return rc;
+  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_denoise: ") + hipGetErrorString(e));
+  if (er != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_denoise: ") + hipGetErrorString(er));
   return VPT_OK;
 }
 

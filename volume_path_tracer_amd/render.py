@@ -265,6 +265,50 @@ class Integrator:
         s.synchronize()
         return (a.cpu().numpy(), t.cpu().numpy()) if tau else a.cpu().numpy()
 
+    def denoise(self, film, m2, guides=(), guide_sigma=None, iterations: int = 4, sigma_l: float = 4.0,
+                rel_floor: float = 1e-3, variance: bool = False, stream=None):
+        """The denoised film of `film` ([H][W][4]) and its moment plane `m2` ([H][W]): the variance-guided a-trous
+        filter of vpt_gpu_denoise, guided by up to four planes `guides` ([H][W] each; render.matte_guides gives the
+        matte's two) with scale `guide_sigma` (None: 0.2 per guide; a number: that for each; or one per guide).
+        Takes device tensors or numpy arrays and returns the same kind (what `film` is); variance=True: (film, var)
+        with the filtered variance of the mean of Y.  The inputs are not changed; the result is an ordinary film.
+        With tensors the call is asynchronous on `stream` (default: the current one), and the tensors must be ready
+        on that stream: what another stream produced has to be ordered before the call by the caller (an event or a
+        synchronize).  numpy inputs are uploaded on `stream` itself.  Calls on different streams of one Integrator are
+        safe: the library runs them one after the other (they share the context's packed planes)."""
+        torch = self.torch
+        as_numpy = not torch.is_tensor(film)
+        if not 1 <= int(iterations) <= 6:
+            raise ValueError("denoise: iterations is 1..6")
+        guides = list(guides)
+        if len(guides) > 4:
+            raise ValueError("denoise: at most 4 guides")
+        H, W = self.cfg.height, self.cfg.width
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+
+        def dev(a, shape):
+            t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float32, order="C"))  # (a copy)
+            t = t.to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"denoise: expected a plane of shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        with torch.cuda.stream(s):
+            f, m = dev(film, (H, W, 4)), dev(m2, (H, W))
+            gs = [dev(g, (H, W)) for g in guides]
+            out = torch.empty_like(f)
+            var = torch.empty_like(m) if variance else None
+        p = capi.DenoiseParams.make(iterations, len(gs), sigma_l, rel_floor, guide_sigma)
+        gp = (C.c_void_p * max(1, len(gs)))(*[g.data_ptr() for g in gs])
+        capi.check(capi.lib().vpt_gpu_denoise(self.h, C.byref(p), C.c_void_p(f.data_ptr()), C.c_void_p(m.data_ptr()),
+                                              gp if gs else None, C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(var.data_ptr()) if variance else None,
+                                              C.c_void_p(int(s.cuda_stream))), "vpt_gpu_denoise")
+        if as_numpy:
+            s.synchronize()
+            return (out.cpu().numpy(), var.cpu().numpy()) if variance else out.cpu().numpy()
+        return (out, var) if variance else out
+
     def trace_jobs(self, jid_begin: int, jid_count: int, capacity: int = 1 << 20, film=None, stream=None):
         """Render jobs and return their Logger events (worker.cpp:16-48) as a numpy array of
         capi.EVENT_DTYPE sorted by (jid, seq).  Raises if more than `capacity` events occur."""
@@ -522,13 +566,15 @@ def run(cfg: capi.Configuration, integrator: Integrator, tp: TileProvider, film:
 
 
 def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, step_waves: int = 64,
-                    max_waves: Optional[int] = None, abs_floor: float = 1e-3, fused: bool = False):
+                    max_waves: Optional[int] = None, abs_floor: float = 1e-3, fused: bool = False,
+                    return_moments: bool = False):
     """Render a frame from zero until every tile's error estimate (Integrator.tile_errors) is at most
     `target_error` or it has `max_waves` waves (None: cfg.num_waves): `min_waves` waves of every tile, then
     `step_waves` more per round of the tiles still above the target (vpt_gpu_render_adaptive).  Each tile's film
     is the uniform frame's after its own wave count, bit for bit.  fused: the one-launch driver
     (vpt_gpu_render_adaptive_fused: a wavefront owns a tile; the same bytes; tiles of at most 256 pixels).
-    -> (film float32[H][W][4], waves uint32[T], err float32[T], info dict)."""
+    -> (film float32[H][W][4], waves uint32[T], err float32[T], info dict); return_moments: the film's moment plane
+    (float32[H][W], what Integrator.denoise wants beside the film) is appended."""
     torch = it.torch
     T = it.cfg.jobs_per_wave()
     film = torch.zeros_like(it.film)
@@ -543,7 +589,34 @@ def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, st
                                          waves.ctypes.data_as(C.POINTER(C.c_uint32)),
                                          err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res),
                                          C.c_void_p(it.stream_handle(None))), name)
+    if return_moments:
+        return film.cpu().numpy(), waves, err, res.as_dict(), m2.cpu().numpy()
     return film.cpu().numpy(), waves, err, res.as_dict()
+
+
+def render_uniform(it: Integrator, moments: bool = True):
+    """The whole frame (cfg.num_waves waves of every tile) from zero as one ordered launch -- the reference's film bit
+    for bit -- with a moment plane attached: -> (film [H][W][4], m2 [H][W]) device tensors (moments=False: the film
+    alone).  The context's previous plane attachment is restored afterwards."""
+    torch = it.torch
+    film = torch.zeros_like(it.film)
+    m2 = torch.zeros((it.cfg.height, it.cfg.width), dtype=torch.float32, device=it.dev) if moments else None
+    torch.cuda.synchronize(it.dev)
+    prev = getattr(it, "_m2", None)
+    it.set_film_moments(m2)
+    try:
+        it.render_waves(1, int(it.cfg.num_waves), film=film)
+        torch.cuda.synchronize(it.dev)
+    finally:
+        it.set_film_moments(prev)
+    return (film, m2) if moments else film
+
+
+def matte_guides(it: Integrator, sub: int = 1):
+    """The denoiser's two guide planes of a volume, numpy float32 [H][W] each, from one coverage pass
+    (render_alpha(sub, tau=True)): [alpha, tau / (1 + tau)] -- the second keeps the thickness where alpha saturates."""
+    alpha, tau = it.render_alpha(sub=sub, tau=True)
+    return [alpha, (tau / (np.float32(1.0) + tau)).astype(np.float32)]
 
 
 def film_to_xyz(film: np.ndarray) -> np.ndarray:
