@@ -262,6 +262,34 @@ int vpt_gpu_set_film_order(vpt_gpu_ctx* ctx, int mode, uint64_t max_bytes);
 int vpt_gpu_film_order_info(const vpt_gpu_ctx* ctx, int* mode, uint64_t* buffer_bytes, uint64_t* ordered_launches,
                             uint64_t* atomic_launches);
 
+/* The stencil pool's layout.  The sparse pool holds one 9-KiB brick of stencils per leaf, found through the cell
+ * table: every trilinear evaluation loads its cell's table entry to learn the leaf's slot, then the stencil -- two
+ * dependent memory waits.  The dense pool holds a brick of the same layout for every cell of the table (leaf bricks
+ * copied; the bricks of cells without a leaf filled with the getValue of every voxel, neighbours included), so a
+ * stencil's address follows from the position alone and the lookup goes.  Every value read is the same bits: films,
+ * records and counters do not depend on the layout.  The dense pool is table cells x 9216 bytes per grid (the 512^3
+ * stand-in: 2.4 GB beside the 0.84-GB sparse pool, which stays resident: the tree walk and points outside the table
+ * read it).  It is expanded on the device from the uploaded tables; nothing more is uploaded.
+ *   VPT_POOL_AUTO (a context's default): dense when the dense bytes of all its grids together are at most the cap --
+ *     vpt_gpu_set_pool_cap's, else 1/8 of the device's memory -- and the allocation succeeds; else sparse, silently
+ *     (vpt_gpu_pool_info tells).  VPT_POOL_DENSE: dense, or VPT_E_NOMEM.  VPT_POOL_SPARSE frees the dense pool.
+ * The environment variable VPT_POOL_LAYOUT (sparse, dense or auto) replaces the default of contexts created while it
+ * is set.  Callable while no feed or frame of the context is open (else VPT_E_STATE); waits for the context's
+ * launches.  Allocating and freeing device memory may wait for the whole device (see the feeds below). */
+enum { VPT_POOL_SPARSE = 0, VPT_POOL_DENSE = 1, VPT_POOL_AUTO = 2 };
+int vpt_gpu_set_pool_layout(vpt_gpu_ctx* ctx, int layout);
+/* The cap VPT_POOL_AUTO compares the dense bytes with (0 = 1/8 of the device's memory).  Read by the next
+ * vpt_gpu_set_pool_layout; changes nothing by itself. */
+int vpt_gpu_set_pool_cap(vpt_gpu_ctx* ctx, uint64_t max_bytes);
+/* *layout: the layout in use (VPT_POOL_SPARSE or VPT_POOL_DENSE); *policy: the one asked for; sparse_bytes[2],
+ * dense_bytes[2]: the pools' resident bytes of the density and the temperature grid (0 for a pool or a grid that is
+ * not there); *expand_ms: what the last expansion's kernels took (HIP events).  Any pointer may be NULL. */
+int vpt_gpu_pool_info(const vpt_gpu_ctx* ctx, int* layout, int* policy, uint64_t* sparse_bytes, uint64_t* dense_bytes,
+                      double* expand_ms);
+/* Debug (tests): copies the dense bricks of the table cells [cell_begin, cell_begin + cell_count) of the density
+ * (grid 0) or temperature (grid 1) grid into out (cell_count x 2304 floats).  VPT_E_STATE without a dense pool. */
+int vpt_gpu_debug_read_pool(vpt_gpu_ctx* ctx, int grid, uint64_t cell_begin, uint64_t cell_count, float* out);
+
 /* A band launch: renders the jobs { (wave_begin + w) * T + t : t in [tile_lo, tile_hi), w in [0, wave_count) } --
  * wave_count waves (0-based) of a band of consecutive tiles -- asynchronously on `hip_stream`, adding into
  * `film_device` (NULL = the context's own film).  It is the partition a multi-GPU frame needs to stay bit-exact:

@@ -135,6 +135,7 @@ VPT_RNG_REFERENCE, VPT_RNG_PIXEL = 0, 1
 VPT_ORDER_JID, VPT_ORDER_COST_WAVE_MAJOR, VPT_ORDER_COST_TILE_MAJOR, VPT_ORDER_COST_TAIL = 0, 1, 2, 3
 VPT_ORDER_COST_SAME_TILE = 4
 VPT_FILM_ATOMIC, VPT_FILM_ORDERED = 0, 1
+VPT_POOL_SPARSE, VPT_POOL_DENSE, VPT_POOL_AUTO = 0, 1, 2
 VPT_GATES_CONTEXT, VPT_GATES_LATENCY, VPT_GATES_FULL = 0, 1, 2
 EVENT_NAMES = ("new_ray", "sampled_point", "null", "scatter_terminated", "scatter", "absorbed")
 
@@ -323,6 +324,12 @@ def lib() -> C.CDLL:
         L.vpt_gpu_set_film_order.argtypes = [vp, C.c_int, C.c_uint64]
         L.vpt_gpu_film_order_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint64),
                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "vpt_gpu_set_pool_layout"):  # (older builds in A/B runs lack the dense pool)
+        L.vpt_gpu_set_pool_layout.argtypes = [vp, C.c_int]
+        L.vpt_gpu_set_pool_cap.argtypes = [vp, C.c_uint64]
+        L.vpt_gpu_pool_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.vpt_gpu_debug_read_pool.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, fp]
     L.vpt_gpu_set_job_order.argtypes = [vp, C.c_int]
     L.vpt_gpu_set_job_order_tail.argtypes = [vp, C.c_int]
     L.vpt_gpu_tile_costs.argtypes = [vp, fp, C.POINTER(C.c_uint32)]

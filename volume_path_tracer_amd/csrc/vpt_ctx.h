@@ -47,8 +47,10 @@ struct DeviceGrid {
   void* cells128 = nullptr;
   void* root = nullptr;
   void* bricks = nullptr;
+  void* dense = nullptr;  // the direct-addressed pool (vpt_gpu_set_pool_layout), dense_bytes of it; dev.dense follows it
   DevGrid dev{};
   size_t bytes = 0;
+  size_t brick_bytes = 0, dense_bytes = 0;
 };
 
 }  // namespace vpt
@@ -187,6 +189,12 @@ struct vpt_gpu_ctx {
   float* frame_film = nullptr;
   // vpt_gpu_create's phases (ms): grid flatten + majorant fix, grid upload, the rest, the tile-cost pass, device bind
   double setup_ms[5] = {};
+  // The stencil pool's layout (vpt_gpu_set_pool_layout): the policy asked for, the cap VPT_POOL_AUTO compares the
+  // dense bytes of the context's grids with (0: 1/8 of the device's memory), and what the last expansion's kernels
+  // took (HIP events, ms).  The layout in use is density.dense != nullptr.
+  int pool_policy = VPT_POOL_AUTO;
+  uint64_t pool_cap = 0;
+  float pool_expand_ms = 0.0f;
 };
 
 // A feed: one launch of the production kernel that renders job ids as the host pushes them (see

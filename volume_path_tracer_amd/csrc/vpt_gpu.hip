@@ -82,6 +82,8 @@ static int upload_grid(const HostGrid& h, DeviceGrid& d) {
   d.dev.cells128 = (const int2*)d.cells128;
   d.dev.root = (const RootTileDev*)d.root;
   d.dev.bricks = (const float*)d.bricks;
+  d.dev.dense = nullptr;
+  d.brick_bytes = h.bricks.size() * sizeof(float);
   return VPT_OK;
 }
 
@@ -92,7 +94,42 @@ static void free_grid(DeviceGrid& d) {
   (void)hipFree(d.cells128);
   (void)hipFree(d.root);
   (void)hipFree(d.bricks);
+  (void)hipFree(d.dense);
   d = DeviceGrid{};
+}
+
+// The direct-addressed pool of an uploaded grid (vpt_gpu_set_pool_layout): table cells x 9216 bytes.
+static uint64_t dense_pool_bytes(const DeviceGrid& d) {
+  if (!d.cells8) return 0;
+  return (uint64_t)d.dev.r8_n[0] * (uint64_t)d.dev.r8_n[1] * (uint64_t)d.dev.r8_n[2] * kBrickVox * sizeof(float);
+}
+
+static void free_dense(DeviceGrid& d) {
+  (void)hipFree(d.dense);
+  d.dense = nullptr;
+  d.dense_bytes = 0;
+  d.dev.dense = nullptr;
+}
+
+// Allocates d's dense pool and enqueues its expansion on the null stream.  VPT_E_NOMEM (nothing allocated) when the
+// device has no room for it.
+static int expand_dense(DeviceGrid& d) {
+  const uint64_t bytes = dense_pool_bytes(d);
+  if (bytes == 0) return VPT_OK;
+  const hipError_t e = hipMalloc(&d.dense, bytes);
+  if (e != hipSuccess) {
+    d.dense = nullptr;
+    (void)hipGetLastError();
+    return set_error(VPT_E_NOMEM, "dense stencil pool: " + std::to_string(bytes >> 20) + " MiB: " + hipGetErrorString(e));
+  }
+  d.dense_bytes = bytes;
+  const uint64_t cells = bytes / (kBrickVox * sizeof(float));
+  DevGrid g = d.dev;
+  g.dense = nullptr;
+  hipLaunchKernelGGL(vpt_dense_expand_kernel, dim3((unsigned)std::min<uint64_t>(cells, 1u << 20)), dim3(256), 0, nullptr,
+                     g, (float*)d.dense, cells);
+  VPT_HIP(hipGetLastError());
+  return VPT_OK;
 }
 
 }  // namespace vpt
@@ -293,6 +330,62 @@ uint64_t ordered_cap(vpt_gpu_ctx* ctx, uint64_t want) {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return ctx->samples_bytes;
   return (uint64_t)(free_b + ctx->samples_bytes) / 4 * 3;
+}
+
+// The stencil pool's layout for `policy` (vpt_gpu_set_pool_layout), the context's launches waited for by the caller:
+// builds or frees the dense pools of the context's grids and points the host copy of the scene at them (the caller
+// pushes it).  VPT_POOL_AUTO never fails for want of memory: it stays sparse.
+int apply_pool_layout(vpt_gpu_ctx* ctx, int policy) {
+  vpt::DeviceGrid* grids[2] = {&ctx->density, ctx->temperature.cells8 || ctx->temperature.bricks ? &ctx->temperature : nullptr};
+  uint64_t need = 0;
+  for (vpt::DeviceGrid* d : grids)
+    if (d) need += vpt::dense_pool_bytes(*d);
+  bool dense = policy == VPT_POOL_DENSE && need > 0;
+  if (policy == VPT_POOL_AUTO && need > 0) {
+    uint64_t cap = ctx->pool_cap;
+    if (cap == 0) {
+      size_t free_b = 0, total_b = 0;
+      VPT_HIP(hipMemGetInfo(&free_b, &total_b));
+      cap = (uint64_t)total_b / 8;
+    }
+    dense = need <= cap;
+  }
+  const bool have = ctx->density.dense != nullptr;
+  int rc = VPT_OK;
+  if (dense && !have) {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    VPT_HIP(hipEventCreate(&ev[0]));
+    VPT_HIP(hipEventCreate(&ev[1]));
+    (void)hipEventRecord(ev[0], nullptr);
+    for (vpt::DeviceGrid* d : grids)
+      if (d && rc == VPT_OK) rc = vpt::expand_dense(*d);
+    (void)hipEventRecord(ev[1], nullptr);
+    const hipError_t e = hipEventSynchronize(ev[1]);
+    if (rc == VPT_OK && e != hipSuccess) rc = vpt::set_error(VPT_E_HIP, std::string("dense stencil pool: ") + hipGetErrorString(e));
+    if (rc == VPT_OK) (void)hipEventElapsedTime(&ctx->pool_expand_ms, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (rc != VPT_OK) {
+      dense = false;
+      if (rc == VPT_E_NOMEM && policy == VPT_POOL_AUTO) rc = VPT_OK;  // (sparse, silently: vpt_gpu_pool_info tells)
+    }
+  }
+  for (vpt::DeviceGrid* d : grids) {
+    if (!d) continue;
+    if (!dense) vpt::free_dense(*d);
+    d->dev.dense = (const float*)d->dense;
+  }
+  ctx->scene.density.dense = ctx->density.dev.dense;
+  ctx->scene.temperature.dense = ctx->temperature.dev.dense;
+  return rc;
+}
+
+// A context's first layout: VPT_POOL_AUTO, or what the environment variable VPT_POOL_LAYOUT names.
+int default_pool_policy() {
+  const char* v = std::getenv("VPT_POOL_LAYOUT");
+  if (v && !std::strcmp(v, "sparse")) return VPT_POOL_SPARSE;
+  if (v && !std::strcmp(v, "dense")) return VPT_POOL_DENSE;
+  return VPT_POOL_AUTO;
 }
 
 }  // namespace
@@ -737,6 +830,11 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   vpt::scene_finalize(ctx->scene);  // uses only the density map (host copy of the values)
   ctx->scene.temperature = ctx->temperature.dev;
   ctx->scene.has_temperature = has_temperature ? 1 : 0;
+  // The direct-addressed stencil pool, expanded on the device from the tables just uploaded (part of the upload's
+  // lap; its kernels' own time: vpt_gpu_pool_info).
+  ctx->pool_policy = default_pool_policy();
+  if ((rc = apply_pool_layout(ctx.get(), ctx->pool_policy))) return rc;
+  lap(1);
   ctx->scene.bb_lds_ok = has_temperature ? vpt::blackbody_rows_suffice(grids.temp_range, cfg->volume_parameters.temperature_scale,
                                                                     cfg->volume_parameters.temperature_offset, vpt::kBbLdsRows)
                                      : 0;
@@ -1408,6 +1506,51 @@ int vpt_gpu_kernel_variant(const vpt_gpu_ctx* ctx, int* has_temperature, int* ru
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "null context");
   if (has_temperature) *has_temperature = ctx->scene.has_temperature ? 1 : 0;
   if (run_skipping) *run_skipping = ctx->use_runs ? 1 : 0;
+  return VPT_OK;
+}
+
+int vpt_gpu_set_pool_layout(vpt_gpu_ctx* ctx, int layout) {
+  if (!ctx || layout < VPT_POOL_SPARSE || layout > VPT_POOL_AUTO)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_pool_layout: bad argument");
+  if (ctx->open_feeds.load() > 0) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_pool_layout: a feed of this context is open");
+  if (ctx->frame_waves) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_pool_layout: a frame is open");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if ((rc = wait_ctx(ctx))) return rc;  // (launches in flight read the pool about to change)
+  VPT_HIP(hipDeviceSynchronize());      // (launches on the caller's streams and the null stream too)
+  ctx->pool_policy = layout;
+  rc = apply_pool_layout(ctx, layout);
+  const int prc = push_scene(ctx);
+  return rc ? rc : prc;
+}
+
+int vpt_gpu_set_pool_cap(vpt_gpu_ctx* ctx, uint64_t max_bytes) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_pool_cap: null context");
+  ctx->pool_cap = max_bytes;
+  return VPT_OK;
+}
+
+int vpt_gpu_pool_info(const vpt_gpu_ctx* ctx, int* layout, int* policy, uint64_t* sparse_bytes, uint64_t* dense_bytes,
+                      double* expand_ms) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "null context");
+  if (layout) *layout = ctx->density.dense ? VPT_POOL_DENSE : VPT_POOL_SPARSE;
+  if (policy) *policy = ctx->pool_policy;
+  if (sparse_bytes) sparse_bytes[0] = ctx->density.brick_bytes, sparse_bytes[1] = ctx->temperature.brick_bytes;
+  if (dense_bytes) dense_bytes[0] = ctx->density.dense_bytes, dense_bytes[1] = ctx->temperature.dense_bytes;
+  if (expand_ms) *expand_ms = ctx->pool_expand_ms;
+  return VPT_OK;
+}
+
+int vpt_gpu_debug_read_pool(vpt_gpu_ctx* ctx, int grid, uint64_t cell_begin, uint64_t cell_count, float* out) {
+  if (!ctx || !out || grid < 0 || grid > 1) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_debug_read_pool: bad argument");
+  const vpt::DeviceGrid& d = grid ? ctx->temperature : ctx->density;
+  if (!d.dense) return vpt::set_error(VPT_E_STATE, "vpt_gpu_debug_read_pool: the grid has no dense pool");
+  const uint64_t brick = vpt::kBrickVox * sizeof(float), cells = d.dense_bytes / brick;
+  if (cell_begin > cells || cell_count > cells - cell_begin)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_debug_read_pool: cells outside the table");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (cell_count) VPT_HIP(hipMemcpy(out, (const char*)d.dense + cell_begin * brick, cell_count * brick, hipMemcpyDeviceToHost));
   return VPT_OK;
 }
 

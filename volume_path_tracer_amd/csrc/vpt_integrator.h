@@ -49,6 +49,10 @@ struct DevGrid {
   const int2* cells128;
   const RootTileDev* root;
   const float* bricks;  // [leaf][y 8][z 8][x 9][4]: per voxel row the 2x2 squares of its stencils (see brick_index)
+  // The direct-addressed pool (vpt_gpu_set_pool_layout), or nullptr: a brick of the same layout for every cell of
+  // the cells8 table, [r8 cell index][y 8][z 8][x 9][4], so a stencil's address follows from the position alone
+  // (dense_index).  Expanded on the device from the tables above (vpt_dense_expand_kernel); host builds leave it null.
+  const float* dense;
 };
 
 // Stencil pool of square rows: per leaf and voxel row (y, z) in 0..7, the 2x2 (dy, dz) squares of
@@ -63,6 +67,12 @@ struct DevGrid {
 constexpr int kBrickVox = 576 * 4;
 __host__ __device__ __forceinline__ int64_t brick_index(int32_t code, int32_t i, int32_t j, int32_t k) {
   return ((int64_t)code * 576 + ((j & 7) * 8 + (k & 7)) * 9 + (i & 7)) * 4;
+}
+// The same brick layout in the direct-addressed pool (DevGrid::dense): the cell's index in the cells8 table
+// (mad_index, < 2^32) in place of the leaf code.  The table's origin is a multiple of 128, so i & 7 is the
+// voxel's offset in its table cell.
+__host__ __device__ __forceinline__ int64_t dense_index(uint32_t cell, int32_t i, int32_t j, int32_t k) {
+  return (int64_t)(((uint64_t)cell * 576u + (uint32_t)(((j & 7) * 8 + (k & 7)) * 9 + (i & 7))) * 4u);
 }
 
 struct Cell {
@@ -234,6 +244,21 @@ __host__ __device__ __forceinline__ void fetch_stencil(const DevGrid& g, Cell c,
   }
 }
 
+// The direct-addressed pool's expansion, one 2x2 square at a time: square s (0..575: row (y, z) = s / 9, x = s % 9,
+// brick_index's order) of table cell (a, b, c) is getValue at (x, y + dy, z + dz) from the cell's origin, corner
+// dy<<1 | dz -- for a leaf cell the floats of its sparse brick, for any other cell what fetch_stencil's eight
+// value_at calls return (tile value, background or a neighbouring leaf's voxel).  x = 8, y + 1 = 8 and z + 1 = 8
+// reach into the next cells, past the table's last row too: value_at resolves those through the upper levels.
+__host__ __device__ __forceinline__ void dense_square(const DevGrid& g, int32_t a, int32_t b, int32_t c, int32_t s,
+                                                      float out[4]) {
+  const int32_t x = s % 9, yz = s / 9;
+  const int32_t i = g.r8_org[0] + a * 8 + x, j = g.r8_org[1] + b * 8 + (yz >> 3), k = g.r8_org[2] + c * 8 + (yz & 7);
+  out[0] = value_at(g, i, j, k);
+  out[1] = value_at(g, i, j, k + 1);
+  out[2] = value_at(g, i, j + 1, k);
+  out[3] = value_at(g, i, j + 1, k + 1);
+}
+
 // TrilinearSampler::sample: lerp(a, b, w) = a + w * (b - a), z then y then x.
 __host__ __device__ __forceinline__ float lerpf(float a, float b, float w) { return a + w * (b - a); }
 // Returns true when the cell differs from the previous evaluation (a NanoVDB stencil refresh).
@@ -244,6 +269,23 @@ __host__ __device__ __forceinline__ bool trilinear(const DevGrid& g, StencilCell
   float u = x - fi, v = y - fj, w = z - fk;
   int32_t i = (int32_t)fi, j = (int32_t)fj, k = (int32_t)fk;
   bool refresh = i != last.i || j != last.j || k != last.k;
+  if (g.dense) {
+    // Direct-addressed pool: inside the cells8 table (cell_at's bounds test) the stencil's address follows from
+    // the position -- no cell lookup in front of the fetch, one memory wait instead of two in series.  The brick
+    // of a cell without a leaf holds the eight value_at results fetch_stencil would gather, so the value is the
+    // same bits.  No leaf code is learned: the next evaluation outside the table looks its cell up (code -1).
+    const int32_t a = (i - g.r8_org[0]) >> 3, b = (j - g.r8_org[1]) >> 3, c = (k - g.r8_org[2]) >> 3;
+    if ((uint32_t)a < (uint32_t)g.r8_n[0] && (uint32_t)b < (uint32_t)g.r8_n[1] && (uint32_t)c < (uint32_t)g.r8_n[2]) {
+      const float4* p = reinterpret_cast<const float4*>(g.dense + dense_index(mad_index(a, b, c, g.r8_n), i, j, k));
+      const float4 lo = p[0], hi = p[1];
+      last.i = i;
+      last.j = j;
+      last.k = k;
+      last.code = -1;
+      out = lerpf(lerpf(lerpf(lo.x, lo.y, w), lerpf(lo.z, lo.w, w), v), lerpf(lerpf(hi.x, hi.y, w), lerpf(hi.z, hi.w, w), v), u);
+      return refresh;
+    }
+  }
   const int32_t dx = (i ^ last.i) | (j ^ last.j) | (k ^ last.k);
   const bool same_leaf = last.code >= 0 && dx >= 0 && dx < 8;  // same 8^3 cell as a leaf-backed stencil
   Cell c;
@@ -1000,6 +1042,14 @@ __host__ __device__ __forceinline__ void primary_event(ScenePtr sp, const DevSce
     } else {
       if (Debug) env.tally(CNT_SCATTERS, 1);
       // The next primary ray starts at the scatter point (worker.cpp:179): keep it in ro.
+      if (HasTemp) {
+        // cp again, by the same operations from the lane's ray and s_t0 (eval_collision's pi, untouched since):
+        // held in three VGPRs across the temperature lookup instead, it cost the 80-VGPR kernel scratch once the
+        // lookup had two paths.  local_value keeps the compiler from reusing the first computation.
+        const DevScene Sr = *opaque(sp);
+        const float t = local_value(ln.s_t0);
+        map_fwd(Sr.density, ln.e[0] + ln.d[0] * t, ln.e[1] + ln.d[1] * t, ln.e[2] + ln.d[2] * t, cp[0], cp[1], cp[2]);
+      }
       for (int i = 0; i < 3; ++i) lc.ro[i] = cp[i];
       // sample_Ld (worker.cpp:52-90)
       if (S.li_zero) {

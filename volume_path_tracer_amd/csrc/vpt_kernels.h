@@ -1255,6 +1255,29 @@ __global__ void vpt_tile_cost_kernel(const DevScene* scene, float* cost) {
   cost[tile] = c;
 }
 
+// The direct-addressed stencil pool (vpt_gpu_set_pool_layout) of one grid, expanded from its uploaded tables: a
+// block per cell of the cells8 table (grid-stride), a thread per 16-byte square.  A leaf cell copies its sparse
+// brick; any other cell computes its squares with dense_square.  Every square of every brick is written: 576 per
+// cell, `cells` cells, into dense[cells * kBrickVox].  g.dense is not read (the pool is being built).
+__global__ __launch_bounds__(256) void vpt_dense_expand_kernel(DevGrid g, float* dense, uint64_t cells) {
+  const uint64_t ny = (uint64_t)g.r8_n[1], nz = (uint64_t)g.r8_n[2];
+  for (uint64_t cell = blockIdx.x; cell < cells; cell += gridDim.x) {
+    const int32_t code = cell8_code(g.cells8[cell].x);
+    float4* dst = reinterpret_cast<float4*>(dense + cell * (uint64_t)kBrickVox);
+    if (code >= 0) {
+      const float4* src = reinterpret_cast<const float4*>(g.bricks + (int64_t)code * kBrickVox);
+      for (int32_t s = (int32_t)threadIdx.x; s < kBrickVox / 4; s += (int32_t)blockDim.x) dst[s] = src[s];
+    } else {
+      const int32_t c = (int32_t)(cell % nz), b = (int32_t)((cell / nz) % ny), a = (int32_t)(cell / (nz * ny));
+      for (int32_t s = (int32_t)threadIdx.x; s < kBrickVox / 4; s += (int32_t)blockDim.x) {
+        float v[4];
+        dense_square(g, a, b, c, s, v);
+        dst[s] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  }
+}
+
 // The coverage pass (vpt_gpu_render_alpha): alpha = 1 - mean exp(-tau) over each pixel's sub-rays, tau by the
 // deterministic march of vpt_alpha.h.  A block is one wavefront that owns up to 64 pixels of one tile, indexed as
 // vpt_band_order_kernel indexes them -- block = (tile slot, chunk of 64 pixels), lane p = pixel p of the chunk -- so

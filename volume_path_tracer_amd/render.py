@@ -387,6 +387,29 @@ class Integrator:
         return {"mode": int(m.value), "buffer_bytes": int(b.value), "ordered_launches": int(o.value),
                 "atomic_launches": int(a.value)}
 
+    def set_pool_layout(self, layout: int, cap_bytes: int | None = None) -> None:
+        """capi.VPT_POOL_AUTO (default: the direct-addressed stencil pool when it fits the cap), VPT_POOL_DENSE or
+        VPT_POOL_SPARSE; `cap_bytes` sets VPT_POOL_AUTO's cap first (0 = 1/8 of the device's memory).  Results never
+        depend on it.  See include/vpt_gpu.h vpt_gpu_set_pool_layout."""
+        if cap_bytes is not None:
+            capi.check(capi.lib().vpt_gpu_set_pool_cap(self.h, int(cap_bytes)), "vpt_gpu_set_pool_cap")
+        capi.check(capi.lib().vpt_gpu_set_pool_layout(self.h, int(layout)), "vpt_gpu_set_pool_layout")
+
+    def pool_info(self) -> dict:
+        """The stencil pool's layout in use, the policy, and both pools' bytes as (density, temperature)."""
+        la, po, ms = C.c_int(), C.c_int(), C.c_double()
+        sp, de = (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        capi.check(capi.lib().vpt_gpu_pool_info(self.h, C.byref(la), C.byref(po), sp, de, C.byref(ms)), "vpt_gpu_pool_info")
+        return {"layout": int(la.value), "policy": int(po.value), "sparse_bytes": (int(sp[0]), int(sp[1])),
+                "dense_bytes": (int(de[0]), int(de[1])), "expand_ms": float(ms.value)}
+
+    def debug_read_pool(self, grid: int, cell_begin: int, cell_count: int) -> np.ndarray:
+        """Debug (tests): the dense bricks of table cells [cell_begin, + cell_count) as float32[cell_count, 2304]."""
+        out = np.empty((int(cell_count), 2304), dtype=np.float32)
+        capi.check(capi.lib().vpt_gpu_debug_read_pool(self.h, int(grid), int(cell_begin), int(cell_count),
+                                                      out.ctypes.data_as(C.POINTER(C.c_float))), "vpt_gpu_debug_read_pool")
+        return out
+
     def set_job_order(self, mode: int) -> None:
         """Scheduling order of whole-wave launches: capi.VPT_ORDER_JID (TileProvider order),
         VPT_ORDER_COST_WAVE_MAJOR, VPT_ORDER_COST_TILE_MAJOR, VPT_ORDER_COST_TAIL or VPT_ORDER_COST_SAME_TILE
