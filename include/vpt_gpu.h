@@ -607,6 +607,11 @@ int vpt_gpu_set_pixel_chunk(vpt_gpu_ctx* ctx, int chunk);
 int vpt_gpu_set_run_skipping(vpt_gpu_ctx* ctx, int mode);
 /* The production kernel the context launches: temperature grid present, run skipping on. */
 int vpt_gpu_kernel_variant(const vpt_gpu_ctx* ctx, int* has_temperature, int* run_skipping);
+/* The instantiation the context's last launch ran (host state only: no wait).  *eval_split: 1 when it evaluates
+ * densities in two halves around the rare blocks (the density-only production launches of the throughput kernels:
+ * plain, run-skipping, feed, band and gang), 0 when whole (temperature, records / events, latency, compacting), -1
+ * before the first launch.  Samples never depend on it. */
+int vpt_gpu_last_launch_variant(const vpt_gpu_ctx* ctx, int* eval_split);
 
 /* Scheduling order of a whole-wave job range (jid_begin and jid_count multiples of T).  Results
  * never depend on it: every job keeps its jid and RNG stream, only the fp32 atomic film-add order

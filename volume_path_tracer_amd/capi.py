@@ -320,6 +320,8 @@ def lib() -> C.CDLL:
         L.vpt_gpu_set_pixel_chunk.argtypes = [vp, C.c_int]
     L.vpt_gpu_set_run_skipping.argtypes = [vp, C.c_int]
     L.vpt_gpu_kernel_variant.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "vpt_gpu_last_launch_variant"):  # (older builds in A/B runs lack it)
+        L.vpt_gpu_last_launch_variant.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "vpt_gpu_set_film_order"):
         L.vpt_gpu_set_film_order.argtypes = [vp, C.c_int, C.c_uint64]
         L.vpt_gpu_film_order_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint64),

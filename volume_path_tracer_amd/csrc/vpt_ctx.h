@@ -107,6 +107,7 @@ struct vpt_gpu_ctx {
   vpt::DevScene* scene_full_dev = nullptr;
   int full_gate[4] = {0, 0, 0, 0};   // gate_min, gate_idle, gate_eval, gate_walk (set at creation)
   int last_gate_set = -1;            // the gate set the last launch read (VPT_GATES_*; vpt_gpu_gate_info)
+  int last_eval_split = -1;          // the last launch ran a split-evaluation instantiation (vpt_gpu_last_launch_variant)
   hipStream_t stream = nullptr;
   bool use_runs = false;             // density-only kernel variant with run skipping (see create)
   int pixel_chunk = 0;               // throughput mode: pixels per work item (0 = auto, see render)

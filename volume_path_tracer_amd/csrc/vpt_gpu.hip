@@ -685,6 +685,8 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   }
   ctx->last_gate_set = scene == ctx->scene_full_dev ? VPT_GATES_FULL
                        : scene == ctx->scene_lat_dev ? VPT_GATES_LATENCY : VPT_GATES_CONTEXT;  // (vpt_gpu_gate_info)
+  // (the instantiation just launched splits the evaluation: a density-only production launch of a throughput kernel)
+  ctx->last_eval_split = vpt::kernel_eval_split(temp, dbg, use_lat) ? 1 : 0;
   VPT_HIP(hipGetLastError());
   const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
   if (band) {  // the film's pixels of the band, in wave order (sample counts included)
@@ -1407,6 +1409,7 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
                                      : vpt::vpt_integrate_kernel<false, false, false, false, false, false, false, true>;
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, ctx->scene_full_dev, ctx->counters);
   ctx->last_gate_set = VPT_GATES_FULL;
+  ctx->last_eval_split = vpt::kernel_eval_split(temp, false, false) ? 1 : 0;
   VPT_HIP(hipGetLastError());
   ++ctx->ordered_launches;
   VPT_HIP(hipMemcpyAsync(waves_T_host, ctx->gang_waves, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1506,6 +1509,12 @@ int vpt_gpu_kernel_variant(const vpt_gpu_ctx* ctx, int* has_temperature, int* ru
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "null context");
   if (has_temperature) *has_temperature = ctx->scene.has_temperature ? 1 : 0;
   if (run_skipping) *run_skipping = ctx->use_runs ? 1 : 0;
+  return VPT_OK;
+}
+
+int vpt_gpu_last_launch_variant(const vpt_gpu_ctx* ctx, int* eval_split) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "null context");
+  if (eval_split) *eval_split = ctx->last_eval_split;
   return VPT_OK;
 }
 

@@ -261,6 +261,35 @@ __host__ __device__ __forceinline__ void dense_square(const DevGrid& g, int32_t 
 
 // TrilinearSampler::sample: lerp(a, b, w) = a + w * (b - a), z then y then x.
 __host__ __device__ __forceinline__ float lerpf(float a, float b, float w) { return a + w * (b - a); }
+// The two halves of trilinear()'s fetch on their own, for the split evaluation (eval_issue / eval_finish).
+// The direct-addressed pool's stencil of the voxel (i, j, k), when the grid has the pool and the voxel's cell lies
+// inside the cells8 table (cell_at's bounds test): its two 16-byte pieces' address, else nullptr.
+__host__ __device__ __forceinline__ const float4* dense_stencil(const DevGrid& g, int32_t i, int32_t j, int32_t k) {
+  if (g.dense) {
+    const int32_t a = (i - g.r8_org[0]) >> 3, b = (j - g.r8_org[1]) >> 3, c = (k - g.r8_org[2]) >> 3;
+    if ((uint32_t)a < (uint32_t)g.r8_n[0] && (uint32_t)b < (uint32_t)g.r8_n[1] && (uint32_t)c < (uint32_t)g.r8_n[2])
+      return reinterpret_cast<const float4*>(g.dense + dense_index(mad_index(a, b, c, g.r8_n), i, j, k));
+  }
+  return nullptr;
+}
+// The stencil of the voxel (i, j, k) through the cell tables and the sparse pool, trilinear()'s lookup path.
+__host__ __device__ __forceinline__ void lookup_stencil(const DevGrid& g, StencilCell& last, int32_t i, int32_t j, int32_t k,
+                                                        float s[8]) {
+  const int32_t dx = (i ^ last.i) | (j ^ last.j) | (k ^ last.k);
+  const bool same_leaf = last.code >= 0 && dx >= 0 && dx < 8;  // same 8^3 cell as a leaf-backed stencil
+  Cell c;
+  if (same_leaf) {
+    c.code = last.code;
+    c.value = 0.0f;  // only read for non-leaf cells, which are never reused (code < 0 -> value_at)
+  } else {
+    c = cell_at(g, i, j, k);
+  }
+  last.i = i;
+  last.j = j;
+  last.k = k;
+  last.code = c.code;
+  fetch_stencil(g, c, i, j, k, s);
+}
 // Returns true when the cell differs from the previous evaluation (a NanoVDB stencil refresh).
 // The leaf-slot lookup is skipped while the corner cell stays in the previous one's 8^3 cell.
 __host__ __device__ __forceinline__ bool trilinear(const DevGrid& g, StencilCell& last, float x, float y, float z,
@@ -528,7 +557,11 @@ enum : int32_t {
 };
 // SM_EVAL: density at s_t0 pending.  SM_NONE: the lane is not sampling (state != ST_SAMPLE); every
 // transition out of ST_SAMPLE sets it, so the walk loop's blocks test sm alone.
-enum : int32_t { SM_NEED_SEG = 0, SM_STEP = 1, SM_DRAW = 2, SM_EVAL = 3, SM_NONE = 4 };
+// SM_FETCHED / SM_FETCHED_LOOKUP (split evaluations only, see eval_issue): the collision's point is fixed (s_t0) and
+// its density pending -- the stencil's two loads in flight (the direct-addressed pool), or no load issued (no pool,
+// or a corner voxel outside its table: eval_finish takes the lookup path).  Both exist only between the two halves
+// of one lane_iteration: no walk, gate count or exchange ever sees them.
+enum : int32_t { SM_NEED_SEG = 0, SM_STEP = 1, SM_DRAW = 2, SM_EVAL = 3, SM_NONE = 4, SM_FETCHED = 5, SM_FETCHED_LOOKUP = 6 };
 // Block ids for the optional SIMT-utilisation profile (env.prof; a no-op unless VPT_PROFILE).
 enum : int32_t {
   PB_ITER = 0, PB_FETCH, PB_PIXEL, PB_RAY, PB_SAMPLE, PB_NEED_SEG, PB_STEP, PB_DRAW, PB_TRILINEAR,
@@ -1067,29 +1100,106 @@ __host__ __device__ __forceinline__ void primary_event(ScenePtr sp, const DevSce
   if (ev != 0) ln.sm = SM_NONE;
 }
 
+// The exact distance of a parked free-flight draw (SM_EVAL), deferred from SM_DRAW
+// (majorant_transmittance_sampler.cpp:44-45): dt = -log(1 - u) / sigma_maj (random.hpp:20-22), t = t0 + dt / m_scale.
+// false: the draw overshoots the segment after all, which is dropped (SM_NEED_SEG); true: s_t0 is the tentative collision.
+template <class Env>
+__host__ __device__ __forceinline__ bool eval_distance(Lane& ln, const LaneCold& lc, Env& env, float sigma_maj) {
+  const float dt_m = -math::logf_glibc_unit(lc.y_draw, env.logf_table()) / sigma_maj;
+  const float tc = ln.s_t0 + math::div_by_recip(dt_m, ln.scale, ln.rscale);  // == dt_m / m_scale
+  if (!(tc < ln.s_t1)) {
+    ln.sm = SM_NEED_SEG;
+    return false;
+  }
+  ln.s_t0 = tc;
+  return true;
+}
+
+template <bool HasTemp, bool Debug, class Env>
+__host__ __device__ __forceinline__ void eval_event(ScenePtr sp, const DevScene& S, const DevGrid& G, Lane& ln, LaneCold& lc, Env& env,
+                                                    float sigma_maj, float pi_x, float pi_y, float pi_z, float dens);
+
 // A tentative collision at s_t0 (SM_EVAL): density, then the primary path's event
 // (worker.cpp:145-188) or the shadow ray's ratio-tracking update (worker.cpp:66-85).
 template <bool HasTemp, bool Debug, class Env>
 __host__ __device__ __forceinline__ void eval_collision(ScenePtr sp, const DevScene& S, const DevGrid& G, Lane& ln, Env& env) {
   LaneCold& lc = env.cold();
   const float sigma_maj = ln.s_dmaj * S.sigma_t;
-  {
-    // The draw's exact free-flight distance, deferred from SM_DRAW (majorant_transmittance_sampler.cpp:44-45):
-    // dt = -log(1 - u) / sigma_maj (random.hpp:20-22), t = t0 + dt / m_scale.
-    const float dt_m = -math::logf_glibc_unit(lc.y_draw, env.logf_table()) / sigma_maj;
-    const float tc = ln.s_t0 + math::div_by_recip(dt_m, ln.scale, ln.rscale);  // == dt_m / m_scale
-    if (!(tc < ln.s_t1)) {  // overshoot after all: drop the segment
-      ln.sm = SM_NEED_SEG;
-      return;
-    }
-    ln.s_t0 = tc;  // the tentative collision
-  }
+  if (!eval_distance(ln, lc, env, sigma_maj)) return;
   env.prof(PB_TRILINEAR);
   const float t = ln.s_t0;
   float pi_x = ln.e[0] + ln.d[0] * t, pi_y = ln.e[1] + ln.d[1] * t, pi_z = ln.e[2] + ln.d[2] * t;
   float dens;
   if (Debug) env.tally(CNT_DENSITY_EVALS, 1);
   env.tally(CNT_STENCILS, trilinear(G, lc.dens_cell, pi_x, pi_y, pi_z, dens) ? 1 : 0);
+  eval_event<HasTemp, Debug>(sp, S, G, ln, lc, env, sigma_maj, pi_x, pi_y, pi_z, dens);
+}
+
+// The split evaluation (environments with kEvalSplit, see env_eval_split): eval_collision cut at the stencil fetch
+// into two halves of one lane_iteration, so that the blocks between them (finish, fetch, pixel) run under the fetch's
+// memory round trip instead of after it (C3 -1.1 %, EXPERIMENTS.md section 20).  eval_issue is the first half: the exact distance, the overshoot test, the collision's point
+// and, with the direct-addressed pool, the stencil's two 16-byte loads into lo / hi -- locals of lane_iteration, live
+// from here to eval_finish only -- with the sampler's cell bookkeeping and the tallies of a lane that carries them.
+// The lane leaves in SM_FETCHED (loads in flight), SM_FETCHED_LOOKUP (none issued) or SM_NEED_SEG (overshoot).
+template <bool Debug, class Env>
+__host__ __device__ __forceinline__ void eval_issue(const DevScene& S, const DevGrid& G, Lane& ln, Env& env, float4& lo, float4& hi) {
+  LaneCold& lc = env.cold();
+  if (!eval_distance(ln, lc, env, ln.s_dmaj * S.sigma_t)) return;
+  env.prof(PB_TRILINEAR);
+  const float t = ln.s_t0;
+  const float pi_x = ln.e[0] + ln.d[0] * t, pi_y = ln.e[1] + ln.d[1] * t, pi_z = ln.e[2] + ln.d[2] * t;
+  const int32_t i = (int32_t)floorf(pi_x), j = (int32_t)floorf(pi_y), k = (int32_t)floorf(pi_z);
+  if (Debug) env.tally(CNT_DENSITY_EVALS, 1);
+  ln.sm = SM_FETCHED_LOOKUP;
+  if (const float4* p = dense_stencil(G, i, j, k)) {
+    lo = p[0];
+    hi = p[1];
+    StencilCell& last = lc.dens_cell;
+    env.tally(CNT_STENCILS, (i != last.i || j != last.j || k != last.k) ? 1 : 0);
+    last.i = i;
+    last.j = j;
+    last.k = k;
+    last.code = -1;
+    ln.sm = SM_FETCHED;
+  }
+}
+
+// The second half, for SM_FETCHED / SM_FETCHED_LOOKUP lanes: the point again from s_t0 (the same operations, so the
+// same bits; held across the blocks between the halves it would cost three registers there), the stencil -- the
+// first use of lo / hi, which is where the wavefront waits for the loads -- or the lookup path's, the lerps of
+// trilinear() and the event.
+template <bool HasTemp, bool Debug, class Env>
+__host__ __device__ __forceinline__ void eval_finish(ScenePtr sp, const DevScene& S, const DevGrid& G, Lane& ln, Env& env,
+                                                     const float4& lo, const float4& hi) {
+  LaneCold& lc = env.cold();
+  const float t = local_value(ln.s_t0);
+  const float pi_x = ln.e[0] + ln.d[0] * t, pi_y = ln.e[1] + ln.d[1] * t, pi_z = ln.e[2] + ln.d[2] * t;
+  const float fi = floorf(pi_x), fj = floorf(pi_y), fk = floorf(pi_z);
+  const float u = pi_x - fi, v = pi_y - fj, w = pi_z - fk;
+  float s[8];
+  if (ln.sm == SM_FETCHED) {
+    s[0] = lo.x;
+    s[1] = lo.y;
+    s[2] = lo.z;
+    s[3] = lo.w;
+    s[4] = hi.x;
+    s[5] = hi.y;
+    s[6] = hi.z;
+    s[7] = hi.w;
+  } else {
+    const int32_t i = (int32_t)fi, j = (int32_t)fj, k = (int32_t)fk;
+    StencilCell& last = lc.dens_cell;
+    env.tally(CNT_STENCILS, (i != last.i || j != last.j || k != last.k) ? 1 : 0);
+    lookup_stencil(G, last, i, j, k, s);
+  }
+  const float dens = lerpf(lerpf(lerpf(s[0], s[1], w), lerpf(s[2], s[3], w), v), lerpf(lerpf(s[4], s[5], w), lerpf(s[6], s[7], w), v), u);
+  eval_event<HasTemp, Debug>(sp, S, G, ln, lc, env, ln.s_dmaj * S.sigma_t, pi_x, pi_y, pi_z, dens);
+}
+
+// The event of a tentative collision at the index point pi with density dens.
+template <bool HasTemp, bool Debug, class Env>
+__host__ __device__ __forceinline__ void eval_event(ScenePtr sp, const DevScene& S, const DevGrid& G, Lane& ln, LaneCold& lc, Env& env,
+                                                    float sigma_maj, float pi_x, float pi_y, float pi_z, float dens) {
   ln.sm = SM_DRAW;  // density <= 0, a null event or an unkilled shadow ray: keep drawing
   if (dens > 0.0f) {
     if (!HasTemp) {
@@ -1238,10 +1348,60 @@ struct env_is_gang<Env, decltype((void)Env::kGang)> {
 // Debug: keep every counter and the job index (per-sample records).
 // ------------------------------------------------------------------------------------------------
 
+// NEE completion (ST_NEE_DONE): the shadow ray's contribution, then the scattered direction and the next bounce.
+template <bool Debug, class Env>
+__host__ __device__ __forceinline__ void nee_done(const DevScene& S, Lane& ln, LaneCold& lc, Env& env) {
+  env.prof(PB_NEE_DONE);
+  if (lc.Tr >= 0.0f) {
+    // p * T_ray * Li with p = HG(w . wi)
+    float c = lc.rd[0] * S.wi[0] + (lc.rd[1] * S.wi[1] + lc.rd[2] * S.wi[2]);
+    float p = hg_eval(S, c);
+    float pt = p * lc.Tr;
+    lc.L[0] = lc.L[0] + pt * S.Li[0];
+    lc.L[1] = lc.L[1] + pt * S.Li[1];
+    lc.L[2] = lc.L[2] + pt * S.Li[2];
+  } else {
+    // L + 0.0f (sample_Ld returned zero): the same value as L for every L but -0.0, which it
+    // turns into +0.0 -- written as a select, so no register holds a constant for it.
+    lc.L[0] = lc.L[0] == 0.0f ? 0.0f : lc.L[0];
+    lc.L[1] = lc.L[1] == 0.0f ? 0.0f : lc.L[1];
+    lc.L[2] = lc.L[2] == 0.0f ? 0.0f : lc.L[2];
+  }
+  float u0 = rng_uniform(ln.rng);
+  float u1 = rng_uniform(ln.rng);
+  if (Debug) env.tally(CNT_RNG_DRAWS, 2);
+  float nd[3];
+  sample_hg(S, lc.rd, u0, u1, nd);
+  for (int i = 0; i < 3; ++i) lc.rd[i] = nd[i];
+  if (Debug) env.event(ln, VPT_EV_SCATTER, lc.ro, lc.rd, 0.0f);
+  ++lc.depth;  // the for-loop increment (worker.cpp:130)
+  ln.shadow = 0;
+  ln.state = ST_RAY;
+}
+
+// Env::kEvalSplit, false for an environment without one: the density evaluation runs as two halves of one
+// lane_iteration (eval_issue / eval_finish).  The kernel turns it on for its density-only production instantiations
+// of the throughput family (vpt_kernels.h kernel_eval_split); every other environment (temperature, records /
+// events, latency, compacting, the host simulator's) compiles the evaluation whole, at the end of the iteration.
+template <class Env, class = void>
+struct env_eval_split {
+  static constexpr bool value = false;
+};
+template <class Env>
+struct env_eval_split<Env, decltype((void)Env::kEvalSplit)> {
+  static constexpr bool value = Env::kEvalSplit;
+};
+
 template <bool HasTemp, bool Debug, bool Runs, class Env>
 __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, Env& env) {
   env.prof(PB_ITER);
   LaneCold& lc = env.cold();
+  constexpr bool kSplit = env_eval_split<Env>::value;
+  // The split evaluation's stencil, in flight from eval_issue to eval_finish: dead outside them (never lane state).
+  float4 st_lo, st_hi;
+#if !defined(__HIP_DEVICE_COMPILE__)
+  st_lo = st_hi = float4{0.0f, 0.0f, 0.0f, 0.0f};
+#endif
   // Every block reads the scene constants it needs afresh (scalar loads behind opaque(), see
   // ScenePtr): nothing stays live in SGPRs across the whole loop, so the walk keeps its own.
   int32_t gate_min;
@@ -1251,7 +1411,21 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
     gate_min = S.gate_min;
     // Lanes of the wavefront sampling right now; rare states run when enough lanes wait for them
     // or the wavefront is short of sampling work (never changes a lane's own operation order).
-    const int32_t n_walking = env.count(ln.state == ST_SAMPLE && ln.sm != SM_EVAL);
+    int32_t n_walking = env.count(ln.state == ST_SAMPLE && ln.sm != SM_EVAL);
+    if constexpr (kSplit) {
+      // The evaluation's gate, decided here instead of at the end of the previous iteration (nothing runs between
+      // the two, so the counts are the ones it read there), and its first half: the stencil loads are issued and
+      // the wavefront goes on to the finish, fetch and pixel blocks; eval_finish, behind them, waits for the loads.
+      const DevGrid& G = S.density;
+      const int32_t n_eval = env.count(ln.state == ST_SAMPLE && ln.sm == SM_EVAL);
+      const bool run_eval = n_eval > 0 && (n_eval >= S.gate_eval || n_walking < S.gate_idle);
+      if (run_eval) wave_priority(kPrioEval);
+      if (run_eval && ln.state == ST_SAMPLE && ln.sm == SM_EVAL) eval_issue<Debug>(S, G, ln, env, st_lo, st_hi);
+      wave_priority(0);
+      // (the lanes just issued sample on: they count as walking, as they did after a whole evaluation)
+      if (run_eval) n_walking += n_eval;
+      env.tick(PT_EVAL);
+    }
     starving = n_walking < S.gate_idle;
   }
   auto go = [&](int32_t st) -> bool {
@@ -1265,41 +1439,12 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
   };
   // Block order follows the state flow so a lane moves on within one pass where it can:
   // NEE completion / film write -> next job / pixel -> ray setup -> walk -> density evaluation.
-
-  {
+  // (split evaluations: NEE completion comes after eval_finish, see there)
+  if constexpr (!kSplit) {
     const DevScene S = *opaque(sp);
-    const DevGrid& G = S.density;
-    (void)G;
-    if (go(ST_NEE_DONE)) {
-      env.prof(PB_NEE_DONE);
-      if (lc.Tr >= 0.0f) {
-        // p * T_ray * Li with p = HG(w . wi)
-        float c = lc.rd[0] * S.wi[0] + (lc.rd[1] * S.wi[1] + lc.rd[2] * S.wi[2]);
-        float p = hg_eval(S, c);
-        float pt = p * lc.Tr;
-        lc.L[0] = lc.L[0] + pt * S.Li[0];
-        lc.L[1] = lc.L[1] + pt * S.Li[1];
-        lc.L[2] = lc.L[2] + pt * S.Li[2];
-      } else {
-        // L + 0.0f (sample_Ld returned zero): the same value as L for every L but -0.0, which it
-        // turns into +0.0 -- written as a select, so no register holds a constant for it.
-        lc.L[0] = lc.L[0] == 0.0f ? 0.0f : lc.L[0];
-        lc.L[1] = lc.L[1] == 0.0f ? 0.0f : lc.L[1];
-        lc.L[2] = lc.L[2] == 0.0f ? 0.0f : lc.L[2];
-      }
-      float u0 = rng_uniform(ln.rng);
-      float u1 = rng_uniform(ln.rng);
-      if (Debug) env.tally(CNT_RNG_DRAWS, 2);
-      float nd[3];
-      sample_hg(S, lc.rd, u0, u1, nd);
-      for (int i = 0; i < 3; ++i) lc.rd[i] = nd[i];
-      if (Debug) env.event(ln, VPT_EV_SCATTER, lc.ro, lc.rd, 0.0f);
-      ++lc.depth;  // the for-loop increment (worker.cpp:130)
-      ln.shadow = 0;
-      ln.state = ST_RAY;
-    }
+    if (go(ST_NEE_DONE)) nee_done<Debug>(S, ln, lc, env);
   }
-  env.tick(PT_NEE);
+  if constexpr (!kSplit) env.tick(PT_NEE);
   {
     const DevScene S = *opaque(sp);
     const DevGrid& G = S.density;
@@ -1478,6 +1623,29 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
     }
   }
   env.tick(PT_PIXEL);
+  if constexpr (kSplit) {
+    // The evaluation's second half, for every lane eval_issue left fetched -- all of them are still here: the early
+    // returns of the fetch and pixel blocks above belong to lanes in ST_FETCH / ST_PIXEL, a fetched lane is in
+    // ST_SAMPLE.  In front of the ray block, whose own vector loads would otherwise wait for the stencil's too;
+    // a lane that scatters flows into that block in this iteration, as it does after a whole evaluation.
+    const DevScene S = *opaque(sp);
+    const DevGrid& G = S.density;
+    const bool fetched = ln.state == ST_SAMPLE && ln.sm >= SM_FETCHED;
+    if (env.count(fetched) > 0) wave_priority(kPrioEval);
+    if (fetched) eval_finish<HasTemp, Debug>(sp, S, G, ln, env, st_lo, st_hi);
+    wave_priority(0);
+    env.tick(PT_EVAL);
+  }
+  if constexpr (kSplit) {
+    // NEE completion, here instead of at the top: a shadow ray the evaluation just killed completes in this
+    // iteration and its path flows into the ray block below, as it does after a whole evaluation.  In front of
+    // eval_issue's loads the block would see those lanes an iteration -- a whole walk loop -- late (measured: C3
+    // 353 ms against the parent's 309, EXPERIMENTS.md section 20).  Absorbed and depth-terminated paths do wait that
+    // iteration for the finish block; on the cloud they are few.
+    const DevScene S = *opaque(sp);
+    if (go(ST_NEE_DONE)) nee_done<Debug>(S, ln, lc, env);
+    env.tick(PT_NEE);
+  }
   {
     const DevScene S = *opaque(sp);
     const DevGrid& G = S.density;
@@ -1609,7 +1777,7 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
     }
   }
   env.tick(PT_WALK);
-  {
+  if constexpr (!kSplit) {  // (split: the lanes parked in SM_EVAL meet their gate at the top of the next iteration)
     const DevScene S = *opaque(sp);
     const DevGrid& G = S.density;
     (void)G;

@@ -138,12 +138,16 @@ constexpr uint32_t kGangMaxArea = 256;
 // job_start and film_add only; every other launch compiles them out.
 // Gang: a gang launch's (vpt_gpu_render_adaptive_fused): the wavefront's fetch is gang_next, film_add stores into the
 // wavefront's scratch; every other launch compiles them out.
-template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false>
+// Split: the density evaluation runs as two halves of one lane_iteration (kEvalSplit, vpt_integrator.h eval_issue);
+// the kernel sets it by kernel_eval_split.
+template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false, bool Split = false>
 struct KernelEnvT {
+  static_assert(!(RegCold && Split), "the latency kernels evaluate whole");
   static_assert(!(RegCold && Feed), "feeds run the throughput kernels only");
   static_assert(!(Band && Feed), "band launches are no feeds");
   static_assert(!(Gang && (RegCold || Feed || Band)), "gang launches run the plain throughput kernels only");
   static constexpr bool kGang = Gang;  // (lane_iteration's fetch block)
+  static constexpr bool kEvalSplit = Split;  // (lane_iteration's evaluation)
   __device__ __forceinline__ ArgsPtr args() const {
     ArgsPtr p = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();  // (KernelArgs is the first argument: offset 0)
     asm volatile("" : "+s"(p));
@@ -777,6 +781,12 @@ __device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc
   }
 }
 
+// The instantiations that split the density evaluation: the density-only production kernels of the throughput
+// family -- plain, run-skipping, feed, band and gang.  The stencil's eight registers fit across the rare blocks of
+// the 72-VGPR kernel only: the temperature kernel (80 VGPRs at 6 waves, none to spare), the records / events kernels
+// and the latency and compacting kernels (the lane's cold state in VGPRs) evaluate whole, with the code they had.
+constexpr bool kernel_eval_split(bool has_temp, bool debug, bool lat) { return !has_temp && !debug && !lat; }
+
 // counters[] order = vpt_counters field order
 template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false,
           bool Gang = false>
@@ -804,7 +814,7 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
     }
     __syncthreads();
   }
-  KernelEnvT<Lat, Feed, Band, Gang> env;
+  KernelEnvT<Lat, Feed, Band, Gang, kernel_eval_split(HasTemp, Debug, Lat)> env;
   env.reg_cold = nullptr;
   Lane ln;
   lane_init(ln);

@@ -368,11 +368,17 @@ class Integrator:
         capi.check(capi.lib().vpt_gpu_latency_kernel_info(self.h, C.byref(m), C.byref(b)), "vpt_gpu_latency_kernel_info")
         return {"mode": int(m.value), "resident_blocks_per_cu": int(b.value)}
 
-    def kernel_variant(self) -> dict:
-        """The production kernel this context launches."""
+    def kernel_variant(self, last_launch: bool = False) -> dict:
+        """The production kernel this context launches.  last_launch: also what the last launch ran -- `eval_split`,
+        True when its instantiation evaluates densities in two halves (None before the first launch)."""
         t, r = C.c_int(), C.c_int()
         capi.check(capi.lib().vpt_gpu_kernel_variant(self.h, C.byref(t), C.byref(r)), "vpt_gpu_kernel_variant")
-        return {"has_temperature": bool(t.value), "run_skipping": bool(r.value)}
+        kv = {"has_temperature": bool(t.value), "run_skipping": bool(r.value)}
+        if last_launch:
+            e = C.c_int()
+            capi.check(capi.lib().vpt_gpu_last_launch_variant(self.h, C.byref(e)), "vpt_gpu_last_launch_variant")
+            kv["eval_split"] = None if e.value < 0 else bool(e.value)
+        return kv
 
     def set_film_order(self, mode: int, max_bytes: int = 0) -> None:
         """capi.VPT_FILM_ORDERED (default: every pixel's samples added in wave order, the reference's film bit
