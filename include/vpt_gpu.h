@@ -217,6 +217,55 @@ int vpt_gpu_destroy(vpt_gpu_ctx* ctx);
 /* Jobs per wave T and total jobs num_waves*T of the context's configuration. */
 int vpt_gpu_job_space(const vpt_gpu_ctx* ctx, uint64_t* jobs_per_wave, uint64_t* total_jobs);
 
+/* ---- sequences: one context, many frames ---------------------------------------------------
+ * A turntable, a fly-through, a look-dev sweep or a simulation sequence renders every frame on one context: the
+ * two calls below replace the scene and the volume in place.  The contract of both: a frame rendered after an
+ * update equals, byte for byte, the frame of a context created fresh with that configuration and those grids.
+ *
+ * Both calls are synchronous: they wait for the context's launches (as vpt_gpu_sync), update, and return with the
+ * new state on the device.  They are NOT concurrent with any other call on the context (no launch, no setter, no
+ * query from another thread while one runs).  Both return VPT_E_STATE while a feed of the context is open or a
+ * drop-in frame is open (vpt_gpu_frame_open), leaving the context untouched.
+ *
+ * What an update keeps: the three gate sets as tuned (vpt_gpu_set_tuning, _set_latency_tuning, _set_full_tuning),
+ * the RNG mode, the latency lanes and the pixel chunk, the stencil pool's policy and cap, the film order and its
+ * sample buffer, the job order mode and tail, a grid set by vpt_gpu_set_tuning, the latency and compaction
+ * settings, the attached moment plane, the denoiser's and the fused adaptive driver's scratch, the context's film
+ * (not cleared), the counters and the uploaded tile list.
+ * What an update drops, because it belongs to the scene that was replaced: the tile costs and ranks -- computed, or
+ * set with vpt_gpu_set_tile_costs -- the band and list ranks filtered from them, and an explicit job permutation
+ * (vpt_gpu_set_job_permutation).  The ranks are recomputed by the next call that needs them (one cost pass, counted
+ * in vpt_gpu_setup_timings' tile-cost entry); their device buffers are reused, so a sequence allocates nothing per
+ * frame.
+ *
+ * vpt_gpu_set_scene: replaces the configuration.  Everything in `cfg` may change -- seed, num_waves (the job space
+ * of vpt_gpu_job_space follows), camera, worker_parameters, volume_parameters -- except output_size and tile_size:
+ * a change of either is VPT_E_INVALID, naming the field.  volume_path and num_workers are ignored.  The new scene
+ * is validated and derived aside first: on any error the context keeps the scene it had and renders it as before.
+ *
+ * vpt_gpu_set_grids: replaces the volume by flattened grids (vpt_grids_flatten; they stay the caller's).  The
+ * configuration is unchanged: a frame that changes both calls vpt_gpu_set_grids, then vpt_gpu_set_scene.  The
+ * temperature grid must be present after the swap exactly if it was before (VPT_E_INVALID otherwise, context
+ * untouched): the kernel family hangs on it.  Re-derived as at creation: the upload, the run-skipping choice
+ * (vpt_gpu_set_run_skipping's -1 follows the new grid, a forced 0 / 1 stays), the occupancy-sized grid (sized, as
+ * at creation, for the kernel the grids choose; a grid set by vpt_gpu_set_tuning stays), the pool's layout under
+ * the kept policy and cap, and the scene constants that read the grids.  The old tables and pools are freed before
+ * the new ones are allocated, so the peak is one volume.  If the call fails after that free (VPT_E_NOMEM for a
+ * volume that does not fit, VPT_POOL_DENSE without room, a HIP error) the context has NO volume: every call that
+ * launches, computes tile costs or derives a scene returns VPT_E_STATE until a later vpt_gpu_set_grids succeeds;
+ * settings, films and vpt_gpu_destroy keep working.
+ *
+ * vpt_gpu_set_grids frees device memory that launches may be reading, so beside the context's own launches it waits
+ * for the whole device (hipDeviceSynchronize, as vpt_gpu_set_pool_layout does): work of OTHER contexts on the same
+ * device is waited for too.  Only this context's feeds are checked -- an open feed of another context on the device
+ * (several contexts of vpt_gpu_create_many on one GPU) blocks the swap until that feed is closed. */
+int vpt_gpu_set_scene(vpt_gpu_ctx* ctx, const vpt_configuration* cfg);
+int vpt_gpu_set_grids(vpt_gpu_ctx* ctx, const vpt_host_grids* grids);
+/* Debug (tests of the contract above): the nth grid upload of vpt_gpu_set_grids from now on (1: the density's of the
+ * next call, 2: the temperature's of a two-grid swap) returns VPT_E_NOMEM as a device without room returns it, after
+ * the old volume was freed; 0 cancels.  One shot. */
+int vpt_gpu_debug_fail_upload(vpt_gpu_ctx* ctx, int nth);
+
 /* Render jobs [jid_begin, jid_begin + jid_count) asynchronously on `hip_stream`
  * (a hipStream_t; NULL = the null stream, as everywhere in HIP), accumulating into `film_device`:
  * a device float[H][W][4] (X, Y, Z, sample count; image.hpp:40-60) — NULL = the context's own
@@ -650,6 +699,9 @@ int vpt_gpu_set_tile_costs(vpt_gpu_ctx* ctx, const float* cost_T);
  * jid_begin + perm[k].  perm must be a permutation of 0..n-1; n = 0 clears it.  Samples never depend
  * on the order.  Not used in the pixel RNG mode. */
 int vpt_gpu_set_job_permutation(vpt_gpu_ctx* ctx, const uint32_t* perm, uint64_t n);
+/* *n: the length of the explicit job permutation in force (0: none -- never set, cleared, or dropped by a scene or
+ * volume update). */
+int vpt_gpu_job_permutation_info(const vpt_gpu_ctx* ctx, uint64_t* n);
 
 int vpt_gpu_sync(vpt_gpu_ctx* ctx);
 

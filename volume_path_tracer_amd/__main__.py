@@ -20,11 +20,19 @@ bit for bit) instead of through the feed, the guides come from one coverage pass
 sub-rays, which also serves ``--alpha``, and ``--alpha-foreground`` applies to the denoised film.
 ``--denoise-iters N`` and ``--denoise-sigma S`` set the iterations (1..6, default 4) and the Y scale (default 4);
 ``--denoised-film-out`` and ``--moments-out`` save the denoised film and the moment plane (.npy); ``--film-out``
-still saves the raw film.  Exits 1 on a fatal error, like vptFATAL.
+still saves the raw film.
+``--frames N`` renders a sequence on one context (Integrator.set_scene / set_volume between frames, DESIGN.md section
+13): ``--orbit DEG`` (default 360) turns the camera about ``look`` around ``up``, ``--camera-path FILE.json`` gives one
+camera per frame ({position, look, up?, vfov_deg?}), ``--volume-sequence PATTERN`` renders the volume file
+``PATTERN % k`` in frame k (read while frame k - 1 is written).  Every output path given must then hold exactly one
+``%d``-style field for the frame index; each frame runs the single frame's code path with the same flags, its files are
+written on a second thread while the next frame renders, and a closing line reports the update time and the total.
+Exits 1 on a fatal error, like vptFATAL.
 """
 from __future__ import annotations
 
 import argparse
+import re
 import sys
 import time
 from pathlib import Path
@@ -36,6 +44,35 @@ def _parse_synth(spec: str):
     if kind not in kinds:
         raise ValueError(f"--synthetic wants constant|cloud|fire[:N], got {spec!r}")
     return kinds[kind][0], int(n or (128 if kind == "constant" else 512)), kinds[kind][1]
+
+
+_FIELD = re.compile(r"%0?\d*d")
+
+
+def _frame_path(pattern: str, k: int) -> str:
+    return pattern % k
+
+
+def _sequence_problem(args, outputs) -> str:
+    """What is wrong with a sequence's arguments ('' if nothing), from the arguments alone."""
+    if args.frames is not None and args.frames < 1:
+        return "--frames wants at least one frame"
+    if args.frames is None and args.camera_path is None:
+        return "--volume-sequence needs --frames N (or a --camera-path, one camera per frame)"
+    if args.orbit is not None and args.camera_path is not None:
+        return "--orbit and --camera-path both move the camera: give one"
+    if args.volume_sequence is not None and args.synthetic:
+        return "--volume-sequence and --synthetic both name the volume: give one"
+    named = dict(outputs)
+    named["--volume-sequence"] = args.volume_sequence
+    for name, p in named.items():
+        if p is None:
+            continue
+        fields = _FIELD.findall(p)
+        if len(fields) != 1 or "%" in _FIELD.sub("", p, count=1):
+            return (f"{name} {p!r}: in a sequence every path holds exactly one %d-style field for the frame index "
+                    f"(e.g. frame_%04d.png)")
+    return ""
 
 
 def main(argv=None) -> int:
@@ -71,13 +108,136 @@ def main(argv=None) -> int:
     ap.add_argument("--denoise-no-guides", action="store_true", help="denoise: do not guide by the matte's planes")
     ap.add_argument("--denoised-film-out", default=None, help="denoise: save the denoised XYZW film (.npy)")
     ap.add_argument("--moments-out", default=None, help="denoise: save the film's moment plane (.npy, float32 [H][W])")
+    ap.add_argument("--frames", type=int, default=None, metavar="N",
+                    help="a sequence of N frames on one context (every output path holds one %%d-style field)")
+    ap.add_argument("--orbit", type=float, default=None, metavar="DEG",
+                    help="sequence: the camera orbits `look` about `up` by DEG degrees over the frames (default 360)")
+    ap.add_argument("--camera-path", default=None, metavar="FILE.json",
+                    help="sequence: one camera per frame, a JSON list of {position, look, up?, vfov_deg?}")
+    ap.add_argument("--volume-sequence", default=None, metavar="PATTERN",
+                    help="sequence: frame k renders the volume file PATTERN %% k (.nvdb or .npz), swapped in place")
     args = ap.parse_args(argv)
     if (args.denoised_film_out or args.moments_out) and not args.denoise:
         ap.error("--denoised-film-out and --moments-out need --denoise")
 
+    # ---- sequences: every output path is a pattern over the frame index (checked before anything touches a device)
+    sequence = args.frames is not None or args.camera_path is not None or args.volume_sequence is not None
+    outputs = {"output_path": args.output_path, "--film-out": args.film_out, "--alpha-out": args.alpha_out,
+               "--waves-out": args.waves_out, "--denoised-film-out": args.denoised_film_out,
+               "--moments-out": args.moments_out, "--event-log": args.event_log}
+    if sequence:
+        problem = _sequence_problem(args, outputs)
+        if problem:
+            print(f"[vpt] FATAL: {problem}", file=sys.stderr)
+            return 1
+    elif args.orbit is not None:
+        ap.error("--orbit needs --frames")
+
     from . import image, traces, volumes
-    from .render import Integrator, TileProvider, matte_guides, render_adaptive, render_uniform, run
-    from .scenes import SynthGrid, read_configuration
+    from .render import Integrator, TileProvider, matte_guides, render_adaptive, render_sequence, render_uniform, run
+    from .scenes import SynthGrid, orbit, read_camera_path, read_configuration, with_camera
+
+    def render_frame(it, tag="", paths=None):
+        """One frame's device work, as the single-frame program does it -> what write_frame saves (host arrays).
+        paths (the single-frame program): each file is written as soon as its data exists, as it always was -- the raw
+        film is on disk before the alpha and denoise passes run; a sequence leaves the files to its writer thread."""
+        cfg = it.cfg
+        res = {"cfg": cfg}
+
+        def emit(piece):
+            if paths is not None:
+                write_piece(piece, res, paths)
+
+        t0 = time.perf_counter()
+        m2 = None
+        if args.adaptive is not None:
+            film, waves, err, info, *plane = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
+                                                             step_waves=args.spp_step, max_waves=cfg.num_waves,
+                                                             fused=args.adaptive_fused, return_moments=args.denoise)
+            m2 = plane[0] if plane else None
+            ms = (time.perf_counter() - t0) * 1e3
+            driver = "one launch (fused)" if args.adaptive_fused else "rounds"
+            print(f"[vpt] {tag}Adaptive rendering ({driver} driver) complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, "
+                  f"target {args.adaptive:g}, "
+                  f"{int(waves.min())}-{int(waves.max())} spp): {info['jobs_rendered']} of {info['jobs_uniform']} jobs "
+                  f"({info['jobs_rendered'] / info['jobs_uniform']:.3f}), {info['rounds']} rounds, "
+                  f"{info['tiles_at_max']} tiles at the cap, max tile error {info['max_error']:.4g}", file=sys.stderr)
+            res["waves"] = waves
+            emit("waves")
+        elif args.denoise:  # the ordered frame with its moment plane (the feed keeps none)
+            film, m2 = (t.cpu().numpy() for t in render_uniform(it))
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
+                  file=sys.stderr)
+        else:
+            tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
+            tp.reset_eta()
+            film = run(cfg, it, tp, batch_jobs=args.batch_jobs)
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
+                  file=sys.stderr)
+        if args.event_log:
+            scratch = it.torch.zeros_like(it.film)  # the traced jobs are not part of the image
+            res["events"] = it.trace_jobs(0, args.event_jobs, film=scratch)
+            emit("events")
+        res["film"] = film
+        emit("film")
+        if args.alpha or args.alpha_foreground or args.alpha_out:
+            if args.denoise and not args.denoise_no_guides:  # one pass serves the matte and the guides
+                guides = matte_guides(it, sub=args.alpha_sub or 1)
+                alpha = guides[0]
+            else:
+                alpha = it.render_alpha(sub=args.alpha_sub)
+            res["alpha"] = alpha
+            emit("alpha")
+        if args.denoise:
+            if args.denoise_no_guides:
+                guides = []
+            elif not (args.alpha or args.alpha_foreground or args.alpha_out):
+                guides = matte_guides(it, sub=args.alpha_sub or 1)
+            res["m2"] = m2
+            emit("m2")
+            t1 = time.perf_counter()
+            res["denoised"] = it.denoise(film, m2, guides, iterations=args.denoise_iters, sigma_l=args.denoise_sigma)
+            ms = (time.perf_counter() - t1) * 1e3
+            print(f"[vpt] {tag}Denoised in {ms:.1f} ms ({args.denoise_iters} iterations, {len(guides)} guides, "
+                  f"sigma {args.denoise_sigma:g})", file=sys.stderr)
+            emit("denoised")
+        emit("png")
+        return res
+
+    PIECES = ("waves", "events", "film", "alpha", "m2", "denoised", "png")
+
+    def write_piece(piece, res, paths):
+        """One of a frame's files, from what render_frame has produced (host work only)."""
+        import numpy as np
+
+        if piece == "waves" and "waves" in res and paths["--waves-out"]:
+            np.save(paths["--waves-out"], res["waves"])
+        elif piece == "events" and "events" in res:
+            traces.write_event_log(res["events"], paths["--event-log"])
+        elif piece == "film" and paths["--film-out"]:
+            np.save(paths["--film-out"], res["film"])
+        elif piece == "alpha" and "alpha" in res and paths["--alpha-out"]:
+            np.save(paths["--alpha-out"], res["alpha"])
+        elif piece == "m2" and args.denoise and paths["--moments-out"]:
+            np.save(paths["--moments-out"], res["m2"])
+        elif piece == "denoised" and args.denoise and paths["--denoised-film-out"]:
+            np.save(paths["--denoised-film-out"], res["denoised"])
+        elif piece == "png":
+            film = res["denoised"] if args.denoise else res["film"]
+            if args.alpha or args.alpha_foreground:
+                alpha = res["alpha"]
+                rgb = image.film_to_image(image.foreground_film(film, alpha, res["cfg"]) if args.alpha_foreground else film)
+                a8 = np.rint(np.float32(255.0) * alpha).astype(np.uint8)
+                image.save_png(paths["output_path"], np.concatenate([rgb, a8[..., None]], axis=2))
+            else:
+                image.save_png(paths["output_path"], image.film_to_image(film))
+
+    def write_frame(res, paths):
+        """A frame's files, in the single frame's order (a sequence runs this on its writer thread)."""
+        for piece in PIECES:
+            write_piece(piece, res, paths)
 
     try:
         config_path = Path(args.config_path).resolve(strict=True)
@@ -94,82 +254,48 @@ def main(argv=None) -> int:
             st = SynthGrid(2, n) if with_temp else None
             keep += [sd, st]
             dens, temp = sd.grid(copy=False), (st.grid(copy=False) if st else None)
+        elif args.volume_sequence:
+            dens, temp = volumes.read_grids(_frame_path(args.volume_sequence, 0))
         else:
             vol = config_path.parent / cfg.volume_path.decode()
             dens, temp = volumes.read_grids(vol)
         if temp is not None and temp.leaf_count:
             print(f"TempMin: {float(temp.leaf_values.min())}, TempMax: {float(temp.leaf_values.max())}")
 
-        it = Integrator(cfg, dens, temp, device=args.device)
-        t0 = time.perf_counter()
-        m2 = None
-        if args.adaptive is not None:
-            film, waves, err, info, *plane = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
-                                                             step_waves=args.spp_step, max_waves=cfg.num_waves,
-                                                             fused=args.adaptive_fused, return_moments=args.denoise)
-            m2 = plane[0] if plane else None
-            ms = (time.perf_counter() - t0) * 1e3
-            driver = "one launch (fused)" if args.adaptive_fused else "rounds"
-            print(f"[vpt] Adaptive rendering ({driver} driver) complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, "
-                  f"target {args.adaptive:g}, "
-                  f"{int(waves.min())}-{int(waves.max())} spp): {info['jobs_rendered']} of {info['jobs_uniform']} jobs "
-                  f"({info['jobs_rendered'] / info['jobs_uniform']:.3f}), {info['rounds']} rounds, "
-                  f"{info['tiles_at_max']} tiles at the cap, max tile error {info['max_error']:.4g}", file=sys.stderr)
-            if args.waves_out:
-                import numpy as np
+        if not sequence:
+            it = Integrator(cfg, dens, temp, device=args.device)
+            render_frame(it, paths=outputs)
+            return 0
 
-                np.save(args.waves_out, waves)
-        elif args.denoise:  # the ordered frame with its moment plane (the feed keeps none)
-            film, m2 = (t.cpu().numpy() for t in render_uniform(it))
-            ms = (time.perf_counter() - t0) * 1e3
-            print(f"[vpt] Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
-                  file=sys.stderr)
+        # ---- a sequence: one Integrator, updated in place between frames (Integrator.set_scene / set_volume)
+        if args.camera_path:
+            cams = read_camera_path(args.camera_path)
+            if args.frames is not None and args.frames != len(cams):
+                raise ValueError(f"--frames {args.frames} but {args.camera_path} holds {len(cams)} cameras")
+            cfgs = [with_camera(cfg, **c) for c in cams]
+        elif args.orbit is not None or not args.volume_sequence:
+            cfgs = orbit(cfg, args.frames, 360.0 if args.orbit is None else args.orbit)
         else:
-            tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
-            tp.reset_eta()
-            film = run(cfg, it, tp, batch_jobs=args.batch_jobs)
-            ms = (time.perf_counter() - t0) * 1e3
-            print(f"[vpt] Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
-                  file=sys.stderr)
-        if args.event_log:
-            scratch = it.torch.zeros_like(it.film)  # the traced jobs are not part of the image
-            traces.write_event_log(it.trace_jobs(0, args.event_jobs, film=scratch), args.event_log)
-        if args.film_out:
-            import numpy as np
+            cfgs = [None] * args.frames  # (the volume alone changes)
+        nframes = len(cfgs)
+        it = Integrator(cfgs[0] if cfgs[0] is not None else cfg, dens, temp, device=args.device)
+        t_seq = time.perf_counter()
 
-            np.save(args.film_out, film)
-        if args.alpha or args.alpha_foreground or args.alpha_out:
-            import numpy as np
+        def frames():
+            yield None, None  # (frame 0: the Integrator as created)
+            for k in range(1, nframes):
+                # (frame k's volume is read here, while the writer thread still saves frame k - 1)
+                vol = volumes.read_grids(_frame_path(args.volume_sequence, k)) if args.volume_sequence else None
+                yield cfgs[k], vol
 
-            if args.denoise and not args.denoise_no_guides:  # one pass serves the matte and the guides
-                guides = matte_guides(it, sub=args.alpha_sub or 1)
-                alpha = guides[0]
-            else:
-                alpha = it.render_alpha(sub=args.alpha_sub)
-            if args.alpha_out:
-                np.save(args.alpha_out, alpha)
-        if args.denoise:
-            import numpy as np
-
-            if args.denoise_no_guides:
-                guides = []
-            elif not (args.alpha or args.alpha_foreground or args.alpha_out):
-                guides = matte_guides(it, sub=args.alpha_sub or 1)
-            if args.moments_out:
-                np.save(args.moments_out, m2)
-            t1 = time.perf_counter()
-            film = it.denoise(film, m2, guides, iterations=args.denoise_iters, sigma_l=args.denoise_sigma)
-            ms = (time.perf_counter() - t1) * 1e3
-            print(f"[vpt] Denoised in {ms:.1f} ms ({args.denoise_iters} iterations, {len(guides)} guides, "
-                  f"sigma {args.denoise_sigma:g})", file=sys.stderr)
-            if args.denoised_film_out:
-                np.save(args.denoised_film_out, film)
-        if args.alpha or args.alpha_foreground:
-            rgb = image.film_to_image(image.foreground_film(film, alpha, cfg) if args.alpha_foreground else film)
-            a8 = np.rint(np.float32(255.0) * alpha).astype(np.uint8)
-            image.save_png(args.output_path, np.concatenate([rgb, a8[..., None]], axis=2))
-        else:
-            image.save_png(args.output_path, image.film_to_image(film))
+        count = iter(range(nframes))
+        stats = render_sequence(it, frames(), lambda i: render_frame(i, f"frame {next(count)}: "),
+                                lambda k, res: write_frame(res, {n: (_frame_path(p, k) if p else p)
+                                                                 for n, p in outputs.items()}))
+        total = (time.perf_counter() - t_seq) * 1e3
+        print(f"[vpt] Sequence complete: {stats['frames']} frames in {total:.0f} ms; scene / volume updates "
+              f"{sum(stats['update_ms']):.1f} ms in all (largest {max(stats['update_ms']):.1f} ms), tile-cost passes "
+              f"{it.setup_timings()['tile_costs']:.1f} ms", file=sys.stderr)
     except Exception as e:  # vptFATAL: message and exit(1)
         print(f"[vpt] FATAL: {e}", file=sys.stderr)
         return 1

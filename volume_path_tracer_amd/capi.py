@@ -272,6 +272,11 @@ def lib() -> C.CDLL:
         L.vpt_gpu_create_from.argtypes = [cfgp, vp, fp, C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
         L.vpt_grids_free.argtypes = [vp]
         L.vpt_grids_free.restype = None
+    if hasattr(L, "vpt_gpu_set_scene"):  # (older builds in A/B runs lack the in-place updates)
+        L.vpt_gpu_set_scene.argtypes = [vp, cfgp]
+        L.vpt_gpu_set_grids.argtypes = [vp, vp]
+        L.vpt_gpu_job_permutation_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.vpt_gpu_debug_fail_upload.argtypes = [vp, C.c_int]
     L.vpt_gpu_destroy.argtypes = [vp]
     L.vpt_gpu_job_space.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.vpt_gpu_render_jobs.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]

@@ -110,6 +110,7 @@ struct vpt_gpu_ctx {
   int last_eval_split = -1;          // the last launch ran a split-evaluation instantiation (vpt_gpu_last_launch_variant)
   hipStream_t stream = nullptr;
   bool use_runs = false;             // density-only kernel variant with run skipping (see create)
+  int runs_mode = -1;                // what vpt_gpu_set_run_skipping asked for (-1 auto): re-applied by vpt_gpu_set_grids
   int pixel_chunk = 0;               // throughput mode: pixels per work item (0 = auto, see render)
   int grid_blocks = 0;               // resident capacity (or the set_tuning override)
   int cus = 1;                       // compute units of the device
@@ -117,6 +118,8 @@ struct vpt_gpu_ctx {
   int order_mode = VPT_DEFAULT_JOB_ORDER;
   int order_tail_waves = 0;        // VPT_ORDER_COST_TAIL: tile-major waves (0 = auto)
   uint32_t* order = nullptr;       // tile ranks by descending cost (device), built on first use
+  bool order_valid = false;        // `order` holds the ranks of the current scene (scene updates keep the buffer)
+  float* cost_dev = nullptr;       // the cost pass's T results (device), allocated with `order`
   std::vector<float> tile_cost;    // host copy of the estimates
   uint32_t* perm = nullptr;        // explicit job order of launches with perm_n jobs (device)
   uint64_t perm_n = 0;
@@ -196,6 +199,14 @@ struct vpt_gpu_ctx {
   int pool_policy = VPT_POOL_AUTO;
   uint64_t pool_cap = 0;
   float pool_expand_ms = 0.0f;
+  // What the scene derivation (derive_scene) reads of the grids besides their device tables, kept for
+  // vpt_gpu_set_scene: whether a temperature grid is present (fixed for the context's life) and its value extremes
+  // (bb_lds_ok).  volume_ok: the grids are uploaded -- false only after a vpt_gpu_set_grids that failed once the old
+  // volume was freed; every call that launches or derives a scene then returns VPT_E_STATE until a swap succeeds.
+  bool has_temperature = false;
+  vpt::ValueRange temp_range{};
+  bool volume_ok = true;
+  int debug_fail_upload = 0;  // vpt_gpu_debug_fail_upload: the n-th grid upload of vpt_gpu_set_grids from now fails (0: none)
 };
 
 // A feed: one launch of the production kernel that renders job ids as the host pushes them (see

@@ -143,6 +143,55 @@ constexpr uint64_t kSpreadLanes = 6;
 
 int wait_ctx(vpt_gpu_ctx* ctx);
 
+// What every call that launches, or derives a scene, returns while the context has no volume (vpt_gpu_set_grids).
+int volume_gone() {
+  return vpt::set_error(VPT_E_STATE, "the context has no volume: a vpt_gpu_set_grids failed after the old volume was "
+                                     "freed (a later vpt_gpu_set_grids that succeeds restores it)");
+}
+
+// The scene of `cfg` on the context's uploaded grids, with the context's overrides: the one derivation of creation
+// (create_on), vpt_gpu_set_scene and vpt_gpu_set_grids.  From cfg: build_scene's constants; from the grids: their
+// descriptors as uploaded (the stencil pool's layout included), scene_finalize's constants (the density map), and
+// bb_lds_ok (the temperature grid's value extremes against cfg's scale and offset); from the context: the blackbody
+// and CIE tables and, read from ctx->scene, what its setters own -- the gates (vpt_gpu_set_tuning), pixel_mode
+// (vpt_gpu_set_rng_mode) and wave_lanes.  Writes S alone, so a failure leaves the context as it was.
+int derive_scene(const vpt_gpu_ctx* ctx, const vpt_configuration& cfg, vpt::DevScene& S) {
+  if (int rc = vpt::build_scene(cfg, S)) return rc;
+  S.density = ctx->density.dev;
+  vpt::scene_finalize(S);  // uses only the density map (host copy of the values)
+  S.temperature = ctx->temperature.dev;
+  S.has_temperature = ctx->has_temperature ? 1 : 0;
+  S.bb_lds_ok = ctx->has_temperature ? vpt::blackbody_rows_suffice(ctx->temp_range, cfg.volume_parameters.temperature_scale,
+                                                                   cfg.volume_parameters.temperature_offset, vpt::kBbLdsRows)
+                                     : 0;
+  S.bb = ctx->bb;
+  S.cie = ctx->cie;
+  S.gate_min = ctx->scene.gate_min;
+  S.gate_idle = ctx->scene.gate_idle;
+  S.gate_eval = ctx->scene.gate_eval;
+  S.gate_walk = ctx->scene.gate_walk;
+  S.pixel_mode = ctx->scene.pixel_mode;
+  S.wave_lanes = ctx->scene.wave_lanes;
+  S.tile_area = (uint32_t)(S.tw * S.th);
+  return VPT_OK;
+}
+
+// The tile costs and everything ranked by them belong to the scene that was replaced: dropped, and recomputed by the
+// next call that needs them (ensure_order).  The device buffers stay.  An explicit job permutation goes too.  The
+// caller has waited for the context's launches.
+void drop_order(vpt_gpu_ctx* ctx) {
+  ctx->order_valid = false;
+  ctx->tile_cost.clear();
+  ctx->tile_rank.clear();
+  ctx->band_rank_lo = ctx->band_rank_hi = 0;
+  ctx->list_ranked = false;
+  if (ctx->perm) {
+    (void)hipFree(ctx->perm);
+    ctx->perm = nullptr;
+    ctx->perm_n = 0;
+  }
+}
+
 // Device copy of the scene constants, which every in-flight launch of this context reads: wait for
 // the context's launches (wait_ctx), copy on the context's stream and wait for the copy (the next
 // render may use another stream).
@@ -225,6 +274,7 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->scene_lat_dev);
   (void)hipFree(ctx->scene_full_dev);
   (void)hipFree(ctx->order);
+  (void)hipFree(ctx->cost_dev);
   (void)hipFree(ctx->band_rank);
   (void)hipFree(ctx->list_dev);
   (void)hipFree(ctx->list_slot_dev);
@@ -251,15 +301,13 @@ int rank_tiles(vpt_gpu_ctx* ctx) {
   for (uint64_t i = 0; i < T; ++i) ctx->tile_rank[i] = (uint32_t)i;
   std::stable_sort(ctx->tile_rank.begin(), ctx->tile_rank.end(),
                    [&](uint32_t a, uint32_t b) { return ctx->tile_cost[a] > ctx->tile_cost[b]; });
-  uint32_t* d = nullptr;
-  VPT_HIP(hipMalloc((void**)&d, T * sizeof(uint32_t)));
-  const hipError_t e = hipMemcpy(d, ctx->tile_rank.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    return vpt::set_error(VPT_E_HIP, std::string("tile order upload: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(ctx->order);
-  ctx->order = d;
+  // The context's one buffer (T is fixed for its life), overwritten in place: every caller has waited for the
+  // launches that read the previous ranks (wait_ctx), so a sequence of scene updates allocates nothing per frame.
+  ctx->order_valid = false;
+  if (!ctx->order) VPT_HIP(hipMalloc((void**)&ctx->order, T * sizeof(uint32_t)));
+  const hipError_t e = hipMemcpy(ctx->order, ctx->tile_rank.data(), T * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("tile order upload: ") + hipGetErrorString(e));
+  ctx->order_valid = true;
   // (band launches' filtered ranks: the context's one buffer, so that no launch allocates)
   if (!ctx->band_rank) VPT_HIP(hipMalloc((void**)&ctx->band_rank, T * sizeof(uint32_t)));
   ctx->band_rank_lo = ctx->band_rank_hi = 0;
@@ -271,9 +319,11 @@ int rank_tiles(vpt_gpu_ctx* ctx) {
   return VPT_OK;
 }
 
-// Tile costs (vpt_tile_cost_kernel) and the descending-cost tile ranks, once per context.
+// Tile costs (vpt_tile_cost_kernel) and the descending-cost tile ranks, once per scene: a context's first call that
+// needs them, and the first one after a scene or volume update dropped them (drop_order).
 int ensure_order(vpt_gpu_ctx* ctx) {
-  if (ctx->order) return VPT_OK;
+  if (ctx->order && ctx->order_valid) return VPT_OK;
+  if (!ctx->volume_ok) return volume_gone();
   const auto t0 = std::chrono::steady_clock::now();
   struct Lap {  // (the cost pass's time, vpt_gpu_setup_timings)
     vpt_gpu_ctx* c;
@@ -283,14 +333,13 @@ int ensure_order(vpt_gpu_ctx* ctx) {
   if (ctx->open_feeds.load() > 0)  // the cost pass and its copy would wait for the feed's launch
     return vpt::set_error(VPT_E_STATE, "tile costs: a feed of this context is open (compute them before)");
   const uint64_t T = ctx->scene.T;
-  float* cost = nullptr;
-  VPT_HIP(hipMalloc((void**)&cost, T * sizeof(float)));
+  if (!ctx->cost_dev) VPT_HIP(hipMalloc((void**)&ctx->cost_dev, T * sizeof(float)));  // (kept: one pass per frame of a sequence)
+  float* const cost = ctx->cost_dev;
   hipLaunchKernelGGL(vpt::vpt_tile_cost_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr,
                      ctx->scene_dev, cost);
   ctx->tile_cost.assign(T, 0.0f);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpy(ctx->tile_cost.data(), cost, T * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(cost);
   if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("tile cost pass: ") + hipGetErrorString(e));
   return rank_tiles(ctx);
 }
@@ -411,6 +460,7 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   int rc = ctx_device(ctx);
   if (rc) return rc;
   if (jid_count == 0) return VPT_OK;
+  if (!ctx->volume_ok) return volume_gone();
   if (feed && (ctx->scene.pixel_mode || records || events))
     return vpt::set_error(VPT_E_INVALID, "render: feeds run the reference RNG mode's production kernels only");
   if (band && (feed || records || events || ctx->scene.pixel_mode || ctx->film_order != VPT_FILM_ORDERED || ctx->frame_waves))
@@ -801,6 +851,43 @@ int build_grids(const vpt_grid_desc* density, const vpt_grid_desc* temperature, 
   return VPT_OK;
 }
 
+// The run-skipping variant as the context's grids choose it (vpt_gpu_set_run_skipping's -1).
+bool auto_run_skipping(const vpt_gpu_ctx* ctx) {
+  return !ctx->has_temperature && ctx->density.run_fraction >= VPT_RUNS_MIN_FRACTION;
+}
+
+// Persistent grid: as many blocks as are resident at once, of the production kernel the grids choose (runs: the
+// run-skipping variant); the latency and the compacting kernel's resident blocks per CU.  A grid set by
+// vpt_gpu_set_tuning stays.
+int size_grid(vpt_gpu_ctx* ctx, bool runs) {
+  const bool has_temperature = ctx->has_temperature;
+  int per_cu = 0, cus = 0;
+  // sized for the production kernel of this scene; the debug variant is launched with the same grid
+  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false>
+                           : (runs ? vpt::vpt_integrate_kernel<false, false, true> : vpt::vpt_integrate_kernel<false, false, false>),
+      vpt::kBlockThreads, 0));
+  VPT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  if (per_cu < 1) per_cu = 1;
+  if (!ctx->grid_user) ctx->grid_blocks = per_cu * cus;
+  int lat_per_cu = 0;
+  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &lat_per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false, true>
+                               : (runs ? vpt::vpt_integrate_kernel<false, false, true, true>
+                                       : vpt::vpt_integrate_kernel<false, false, false, true>),
+      vpt::kBlockThreads, 0));
+  ctx->lat_per_cu = std::max(1, std::min(lat_per_cu, per_cu));
+  int compact_per_cu = 0;
+  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &compact_per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false, true, true>
+                                   : (runs ? vpt::vpt_integrate_kernel<false, false, true, true, true>
+                                           : vpt::vpt_integrate_kernel<false, false, false, true, true>),
+      vpt::kBlockThreads, vpt::kXchgBytes));
+  ctx->compact_per_cu = compact_per_cu;
+  ctx->cus = cus > 0 ? cus : 1;
+  return VPT_OK;
+}
+
 // A context on `device` from grids already flattened (vpt_gpu_create, vpt_gpu_create_many).
 int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float* blackbody_500x3, int device,
               vpt_gpu_ctx** out) {
@@ -819,27 +906,25 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   int rc = ctx_device(ctx.get());
   if (rc) return rc;
   lap(4);
-  if ((rc = vpt::build_scene(*cfg, ctx->scene))) return rc;
+  {  // (the configuration is checked before anything is uploaded)
+    vpt::DevScene probe;
+    if ((rc = vpt::build_scene(*cfg, probe))) return rc;
+  }
   if ((rc = vpt::upload_grid(grids.density, ctx->density))) return rc;
   if (grids.has_temperature && (rc = vpt::upload_grid(grids.temperature, ctx->temperature))) return rc;
   lap(1);
   const bool has_temperature = grids.has_temperature;
+  ctx->has_temperature = has_temperature;
+  ctx->temp_range = grids.temp_range;
   // The run-skipping kernel variant is for grids with large equal-majorant regions (C2's constant
   // cube: 36 % of the interior cells have run radius >= 2; the 512^3 cloud: 4 %, where the variant
   // would cost more than it skips).  vpt_gpu_set_run_skipping overrides the choice.
-  ctx->use_runs = !has_temperature && ctx->density.run_fraction >= VPT_RUNS_MIN_FRACTION;
-  ctx->scene.density = ctx->density.dev;
-  vpt::scene_finalize(ctx->scene);  // uses only the density map (host copy of the values)
-  ctx->scene.temperature = ctx->temperature.dev;
-  ctx->scene.has_temperature = has_temperature ? 1 : 0;
+  ctx->use_runs = auto_run_skipping(ctx.get());
   // The direct-addressed stencil pool, expanded on the device from the tables just uploaded (part of the upload's
   // lap; its kernels' own time: vpt_gpu_pool_info).
   ctx->pool_policy = default_pool_policy();
   if ((rc = apply_pool_layout(ctx.get(), ctx->pool_policy))) return rc;
   lap(1);
-  ctx->scene.bb_lds_ok = has_temperature ? vpt::blackbody_rows_suffice(grids.temp_range, cfg->volume_parameters.temperature_scale,
-                                                                    cfg->volume_parameters.temperature_offset, vpt::kBbLdsRows)
-                                     : 0;
 
   std::vector<float> bb(501 * 3, 0.0f);  // row 500 = 0 (reference reads past its table)
   if (blackbody_500x3)
@@ -849,8 +934,6 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   size_t scratch = 0;
   if ((rc = vpt::upload(bb.data(), bb.size() * sizeof(float), (void**)&ctx->bb, scratch))) return rc;
   if ((rc = vpt::upload(vpt::cie_table(), 471 * 3 * sizeof(float), (void**)&ctx->cie, scratch))) return rc;
-  ctx->scene.bb = ctx->bb;
-  ctx->scene.cie = ctx->cie;
 
   ctx->film_count = (uint64_t)cfg->output_size[0] * (uint64_t)cfg->output_size[1] * 4;
   VPT_HIP(hipMalloc((void**)&ctx->film, ctx->film_count * sizeof(float)));
@@ -865,31 +948,7 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   VPT_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   VPT_HIP(hipEventCreateWithFlags(&ctx->samples_done, hipEventDisableTiming));
 
-  // Persistent grid: as many blocks as are resident at once.
-  int per_cu = 0, cus = 0;
-  // sized for the production kernel of this scene; the debug variant is launched with the same grid
-  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false>
-                           : (ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true> : vpt::vpt_integrate_kernel<false, false, false>),
-      vpt::kBlockThreads, 0));
-  VPT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  if (per_cu < 1) per_cu = 1;
-  ctx->grid_blocks = per_cu * cus;
-  int lat_per_cu = 0;
-  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &lat_per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false, true>
-                               : (ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true>
-                                                : vpt::vpt_integrate_kernel<false, false, false, true>),
-      vpt::kBlockThreads, 0));
-  ctx->lat_per_cu = std::max(1, std::min(lat_per_cu, per_cu));
-  int compact_per_cu = 0;
-  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &compact_per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false, true, true>
-                                   : (ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true, true>
-                                                    : vpt::vpt_integrate_kernel<false, false, false, true, true>),
-      vpt::kBlockThreads, vpt::kXchgBytes));
-  ctx->compact_per_cu = compact_per_cu;
-  ctx->cus = cus > 0 ? cus : 1;
+  if ((rc = size_grid(ctx.get(), ctx->use_runs))) return rc;
   // Scheduling defaults from tools/tune.py sweeps on MI355X (C3, 256 spp): rare states run for >= 6
   // waiting lanes, density evaluations (with the deferred exact draw) for >= 36, everything runs when
   // < 8 lanes are walking; the walk loops while >= 4 lanes walk (r02 sweep: 6:8:36:4 363.7 ms vs
@@ -907,7 +966,11 @@ int create_on(const vpt_configuration* cfg, const HostGrids& grids, const float*
   ctx->scene.gate_walk = has_temperature ? 1 : 4;
   ctx->scene.pixel_mode = 0;
   ctx->scene.wave_lanes = 64;
-  ctx->scene.tile_area = (uint32_t)(ctx->scene.tw * ctx->scene.th);
+  {  // (the defaults above are the context's overrides, which the derivation carries over)
+    vpt::DevScene S;
+    if ((rc = derive_scene(ctx.get(), *cfg, S))) return rc;
+    ctx->scene = S;
+  }
   VPT_HIP(hipMalloc((void**)&ctx->scene_dev, sizeof(vpt::DevScene)));
   VPT_HIP(hipMalloc((void**)&ctx->scene_lat_dev, sizeof(vpt::DevScene)));
   VPT_HIP(hipMalloc((void**)&ctx->scene_full_dev, sizeof(vpt::DevScene)));
@@ -1048,6 +1111,85 @@ int vpt_gpu_destroy(vpt_gpu_ctx* ctx) {
   return VPT_OK;
 }
 
+int vpt_gpu_set_scene(vpt_gpu_ctx* ctx, const vpt_configuration* cfg) {
+  if (!ctx || !cfg) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_scene: null argument");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_scene: a feed of this context is open");
+  if (ctx->frame_waves) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_scene: a frame is open");
+  if (!ctx->volume_ok) return volume_gone();
+  for (int i = 0; i < 2; ++i) {
+    if (cfg->output_size[i] != ctx->cfg.output_size[i])
+      return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_scene: output_size differs from the context's (the film, the "
+                                           "tiles and every buffer sized by them are fixed at creation)");
+    if (cfg->tile_size[i] != ctx->cfg.tile_size[i])
+      return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_scene: tile_size differs from the context's (the job space is "
+                                           "fixed at creation)");
+  }
+  vpt::DevScene S;  // built aside: any error above or here leaves the context's scene as it was
+  if ((rc = derive_scene(ctx, *cfg, S))) return rc;
+  if ((rc = wait_ctx(ctx))) return rc;  // (launches in flight read the scene and the ranks about to change)
+  ctx->scene = S;
+  ctx->cfg = *cfg;
+  drop_order(ctx);
+  return push_scene(ctx);
+}
+
+int vpt_gpu_set_grids(vpt_gpu_ctx* ctx, const vpt_host_grids* grids) {
+  if (!ctx || !grids) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_grids: null argument");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_grids: a feed of this context is open");
+  if (ctx->frame_waves) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_grids: a frame is open");
+  if (grids->has_temperature != ctx->has_temperature)
+    return vpt::set_error(VPT_E_INVALID, ctx->has_temperature
+                                             ? "vpt_gpu_set_grids: the context has a temperature grid and the new volume has none "
+                                               "(the kernel family is chosen at creation)"
+                                             : "vpt_gpu_set_grids: the context has no temperature grid and the new volume has one "
+                                               "(the kernel family is chosen at creation)");
+  if ((rc = wait_ctx(ctx))) return rc;  // (launches in flight read the tables and pools about to be freed)
+  VPT_HIP(hipDeviceSynchronize());      // (launches on the caller's streams and the null stream too)
+  // The old volume goes first, so that the peak is one volume and not two.  From here on a failure leaves the
+  // context without a volume (volume_ok false: no device pointer of the freed tables stays in use).
+  ctx->volume_ok = false;
+  drop_order(ctx);
+  vpt::free_grid(ctx->density);
+  vpt::free_grid(ctx->temperature);
+  ctx->scene.density = ctx->density.dev;
+  ctx->scene.temperature = ctx->temperature.dev;
+  auto fail = [&](int code) {
+    const std::string msg = vpt_last_error();  // (the frees and the push below must not replace the cause)
+    vpt::free_grid(ctx->density);
+    vpt::free_grid(ctx->temperature);
+    ctx->scene.density = ctx->density.dev;
+    ctx->scene.temperature = ctx->temperature.dev;
+    (void)push_scene(ctx);
+    return vpt::set_error(code, "vpt_gpu_set_grids: " + msg + " (the context has no volume now)");
+  };
+  // (vpt_gpu_debug_fail_upload: the n-th upload from the call on is refused as a device without room refuses it)
+  auto upload = [&](const vpt::HostGrid& h, vpt::DeviceGrid& d) {
+    if (ctx->debug_fail_upload > 0 && --ctx->debug_fail_upload == 0)
+      return vpt::set_error(VPT_E_NOMEM, "grid upload: refused (vpt_gpu_debug_fail_upload)");
+    return vpt::upload_grid(h, d);
+  };
+  if ((rc = upload(grids->density, ctx->density))) return fail(rc);
+  if (grids->has_temperature && (rc = upload(grids->temperature, ctx->temperature))) return fail(rc);
+  ctx->temp_range = grids->temp_range;
+  // What creation derives from the grids: the run-skipping choice (a forced one stays), the occupancy-sized grid (of
+  // the kernel the grids choose, as at creation; a grid set by vpt_gpu_set_tuning stays), the pool's layout under the
+  // kept policy and cap, and the scene.
+  const bool auto_runs = auto_run_skipping(ctx);
+  ctx->use_runs = ctx->runs_mode < 0 ? auto_runs : ctx->runs_mode == 1;
+  if ((rc = size_grid(ctx, auto_runs))) return fail(rc);
+  if ((rc = apply_pool_layout(ctx, ctx->pool_policy))) return fail(rc);
+  vpt::DevScene S;
+  if ((rc = derive_scene(ctx, ctx->cfg, S))) return fail(rc);
+  ctx->scene = S;
+  if ((rc = push_scene(ctx))) return fail(rc);
+  ctx->volume_ok = true;
+  return VPT_OK;
+}
+
 int vpt_gpu_job_space(const vpt_gpu_ctx* ctx, uint64_t* jobs_per_wave, uint64_t* total_jobs) {
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "null context");
   if (jobs_per_wave) *jobs_per_wave = ctx->scene.T;
@@ -1130,6 +1272,7 @@ int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, fl
   if (rc) return rc;
   if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
     return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_alpha: a feed of this context is open");
+  if (!ctx->volume_ok) return volume_gone();
   if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
   const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
   if (blocks >= (1ULL << 31)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: 2^31 or more pixel chunks");
@@ -1361,6 +1504,7 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
   if (ctx->open_feeds.load() > 0)  // (the call allocates and waits for its launch, which would wait for the feed's)
     return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: a feed of this context is open");
   const uint32_t T = (uint32_t)ctx->scene.T;
+  if (!ctx->volume_ok) return volume_gone();
   if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks; allocates tile_err with them)
   // The full resident grid of the throughput kernel; every wavefront has a scratch slot of one group's samples.
   const uint32_t blocks = (uint32_t)ctx->grid_blocks;
@@ -1457,6 +1601,7 @@ int vpt_gpu_majorant_trace(vpt_gpu_ctx* ctx, const float origin[3], const float 
     return vpt::set_error(VPT_E_INVALID, "vpt_gpu_majorant_trace: bad argument");
   int rc = ctx_device(ctx);
   if (rc) return rc;
+  if (!ctx->volume_ok) return volume_gone();
   float* rows = nullptr;
   int* n = nullptr;
   VPT_HIP(hipMalloc((void**)&rows, (size_t)(max_rows > 0 ? max_rows : 1) * 9 * sizeof(float)));
@@ -1501,7 +1646,8 @@ int vpt_gpu_set_run_skipping(vpt_gpu_ctx* ctx, int mode) {
   if (!ctx || mode < -1 || mode > 1) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_run_skipping: bad argument");
   if (mode == 1 && ctx->scene.has_temperature)
     return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_run_skipping: no run-skipping variant with a temperature grid");
-  ctx->use_runs = mode < 0 ? (!ctx->scene.has_temperature && ctx->density.run_fraction >= VPT_RUNS_MIN_FRACTION) : mode == 1;
+  ctx->runs_mode = mode;  // (kept: vpt_gpu_set_grids re-derives "auto" from the new grid, a forced choice stays)
+  ctx->use_runs = mode < 0 ? auto_run_skipping(ctx) : mode == 1;
   return VPT_OK;
 }
 
@@ -1616,6 +1762,7 @@ int vpt_gpu_set_tile_costs(vpt_gpu_ctx* ctx, const float* cost) {
   if (!ctx || !cost) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_tile_costs: null argument");
   int rc = ctx_device(ctx);
   if (rc) return rc;
+  if (!ctx->volume_ok) return volume_gone();  // (costs describe a scene, and there is none to render)
   for (uint64_t i = 0; i < ctx->scene.T; ++i)  // NaN would break the sort's strict weak ordering
     if (!std::isfinite(cost[i])) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_tile_costs: non-finite cost");
   if ((rc = wait_ctx(ctx))) return rc;  // in-flight launches read the current order
@@ -1641,6 +1788,18 @@ int vpt_gpu_set_job_permutation(vpt_gpu_ctx* ctx, const uint32_t* perm, uint64_t
   VPT_HIP(hipMalloc((void**)&ctx->perm, n * sizeof(uint32_t)));
   VPT_HIP(hipMemcpy(ctx->perm, perm, n * sizeof(uint32_t), hipMemcpyHostToDevice));
   ctx->perm_n = n;
+  return VPT_OK;
+}
+
+int vpt_gpu_job_permutation_info(const vpt_gpu_ctx* ctx, uint64_t* n) {
+  if (!ctx || !n) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_job_permutation_info: null argument");
+  *n = ctx->perm ? ctx->perm_n : 0;
+  return VPT_OK;
+}
+
+int vpt_gpu_debug_fail_upload(vpt_gpu_ctx* ctx, int nth) {
+  if (!ctx || nth < 0) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_debug_fail_upload: bad argument");
+  ctx->debug_fail_upload = nth;
   return VPT_OK;
 }
 

@@ -151,6 +151,45 @@ class Integrator:
         capi.check(capi.lib().vpt_gpu_setup_timings(self.h, ms, 5), "vpt_gpu_setup_timings")
         return dict(zip(("flatten_fix", "upload", "rest", "tile_costs", "bind"), (float(x) for x in ms)))
 
+    # ---- sequences: in-place updates (include/vpt_gpu.h "sequences") -------------------------------------------
+    def _refresh(self, cfg: capi.Configuration) -> None:
+        self.cfg = cfg
+        jpw, tot = C.c_uint64(), C.c_uint64()
+        capi.check(capi.lib().vpt_gpu_job_space(self.h, C.byref(jpw), C.byref(tot)), "vpt_gpu_job_space")
+        self.jobs_per_wave, self.total_jobs = int(jpw.value), int(tot.value)
+
+    def set_scene(self, cfg: capi.Configuration) -> None:
+        """Replace the configuration in place (vpt_gpu_set_scene): everything but output_size and tile_size may
+        change.  Synchronous; the next frame equals a fresh Integrator's for `cfg`, byte for byte.  Tuning, RNG mode,
+        pool layout, film and job order settings stay; tile costs (computed or set) and a job permutation are
+        dropped.  self.film is kept (not cleared).  On an error the Integrator renders its previous scene."""
+        c = cfg.copy()
+        capi.check(capi.lib().vpt_gpu_set_scene(self.h, C.byref(c)), "vpt_gpu_set_scene")
+        self._refresh(c)
+
+    def set_camera(self, position=None, look=None, up=None, vfov_deg=None) -> None:
+        """set_scene with the camera fields given replaced (the others, and the rest of the scene, as they are)."""
+        from .scenes import with_camera
+
+        self.set_scene(with_camera(self.cfg, position, look, up, vfov_deg))
+
+    def set_volume(self, density, temperature=None) -> None:
+        """Replace the volume in place (vpt_grids_flatten + vpt_gpu_set_grids); the configuration stays.  A
+        temperature grid must be given exactly if the Integrator was created with one.  Synchronous.  If the swap
+        fails after the old volume was freed the Integrator has no volume until a later set_volume succeeds (every
+        render raises, VPT_E_STATE)."""
+        L = capi.lib()
+        dens_desc = density.desc if hasattr(density, "desc") else density
+        temp_desc = None if temperature is None else (temperature.desc if hasattr(temperature, "desc") else temperature)
+        g = C.c_void_p()
+        capi.check(L.vpt_grids_flatten(C.byref(dens_desc), C.byref(temp_desc) if temp_desc is not None else None,
+                                       C.byref(g)), "vpt_grids_flatten")
+        try:
+            capi.check(L.vpt_gpu_set_grids(self.h, g), "vpt_gpu_set_grids")
+        finally:
+            L.vpt_grids_free(g)
+        self._refresh(self.cfg)
+
     def __del__(self):
         try:
             if getattr(self, "h", None):
@@ -449,6 +488,12 @@ class Integrator:
         capi.check(capi.lib().vpt_gpu_set_job_permutation(self.h, p.ctypes.data_as(C.POINTER(C.c_uint32)), p.size),
                    "vpt_gpu_set_job_permutation")
 
+    def job_permutation_size(self) -> int:
+        """Length of the explicit job permutation in force (0: none; a scene or volume update drops it)."""
+        n = C.c_uint64()
+        capi.check(capi.lib().vpt_gpu_job_permutation_info(self.h, C.byref(n)), "vpt_gpu_job_permutation_info")
+        return int(n.value)
+
     def counters(self, reset: bool = False) -> dict:
         c = capi.Counters()
         capi.check(capi.lib().vpt_gpu_counters(self.h, C.byref(c), 1 if reset else 0), "vpt_gpu_counters")
@@ -639,6 +684,75 @@ def render_uniform(it: Integrator, moments: bool = True):
     finally:
         it.set_film_moments(prev)
     return (film, m2) if moments else film
+
+
+def _host_copy(x, torch):
+    """x with every device tensor in it (tuples, lists and dicts walked) replaced by a numpy copy."""
+    if torch.is_tensor(x):
+        return x.detach().cpu().numpy()
+    if isinstance(x, tuple):
+        return tuple(_host_copy(v, torch) for v in x)
+    if isinstance(x, list):
+        return [_host_copy(v, torch) for v in x]
+    if isinstance(x, dict):
+        return {k: _host_copy(v, torch) for k, v in x.items()}
+    return x
+
+
+def render_sequence(it: Integrator, frames, render_frame, sink, depth: int = 2) -> dict:
+    """Render a sequence on one Integrator.  `frames` yields (cfg or None, (density, temperature) or None) per frame:
+    what changes before it -- the volume first (Integrator.set_volume), then the scene (Integrator.set_scene); (None,
+    None) renders the Integrator as it stands.  `render_frame(it)` returns what one frame produces (a film, a tuple of
+    planes, ...); device tensors in it are copied to the host here, because the Integrator's buffers serve the next
+    frame.  `sink(index, result)` runs on one writer thread behind a queue of `depth` frames, so frame k is converted
+    and encoded while frame k + 1 renders; its indices arrive in order.  An exception of the sink ends the sequence
+    and is raised here.  -> {"frames", "update_ms": [...], "render_ms": [...], "total_ms"} (update: the two set_ calls;
+    render: render_frame and the host copy)."""
+    import queue
+
+    q: "queue.Queue" = queue.Queue(maxsize=max(1, int(depth)))
+    failed: list = []
+
+    def writer():
+        while True:
+            item = q.get()
+            if item is None:
+                return
+            if failed:
+                continue  # (drain, so that the producer never blocks on a full queue)
+            try:
+                sink(*item)
+            except BaseException as e:  # noqa: BLE001 -- re-raised by the caller's thread
+                failed.append(e)
+
+    th = threading.Thread(target=writer, name="vpt-sequence-writer", daemon=True)
+    th.start()
+    update_ms, render_ms = [], []
+    t_begin = time.perf_counter()
+    n = 0
+    try:
+        for cfg, vol in frames:
+            if failed:
+                break
+            t0 = time.perf_counter()
+            if vol is not None:
+                it.set_volume(*vol)
+            if cfg is not None:
+                it.set_scene(cfg)
+            t1 = time.perf_counter()
+            result = _host_copy(render_frame(it), it.torch)
+            t2 = time.perf_counter()
+            update_ms.append((t1 - t0) * 1e3)
+            render_ms.append((t2 - t1) * 1e3)
+            q.put((n, result))
+            n += 1
+    finally:
+        q.put(None)
+        th.join()
+    if failed:
+        raise failed[0]
+    return {"frames": n, "update_ms": update_ms, "render_ms": render_ms,
+            "total_ms": (time.perf_counter() - t_begin) * 1e3}
 
 
 def matte_guides(it: Integrator, sub: int = 1):

@@ -42,6 +42,80 @@ def scene(name: str) -> capi.Configuration:
     return read_configuration(SCENE_DIR / f"{name}.json")
 
 
+def orbit(cfg: capi.Configuration, frames: int, degrees: float = 360.0) -> list:
+    """A turntable: `frames` configurations, frame k with the camera position rotated by degrees * k / frames about the
+    axis through `look` along the normalised `up` (right-handed); look, up, vfov and everything else are cfg's.
+    Frame 0 is cfg's camera bit for bit, and a full turn does not repeat it at the end (frame `frames` would).  The
+    rotation is computed in float64 and rounded once to the configuration's floats."""
+    import numpy as np
+
+    frames = int(frames)
+    if frames < 1:
+        raise ValueError("orbit: at least one frame")
+    cp = cfg.camera_parameters
+    pos, look, up = (np.asarray(v[:], np.float64) for v in (cp.position, cp.look, cp.up))
+    n = float(np.sqrt(up @ up))
+    if not n > 0.0 or not np.isfinite(n):
+        raise ValueError("orbit: the camera's up vector has no direction")
+    axis, r = up / n, pos - look
+    out = []
+    for k in range(frames):
+        c = cfg.copy()
+        a = np.radians(float(degrees) * k / frames)
+        if a != 0.0:  # Rodrigues' rotation of the offset from `look`
+            p = look + r * np.cos(a) + np.cross(axis, r) * np.sin(a) + axis * (axis @ r) * (1.0 - np.cos(a))
+            c.camera_parameters.position[:] = [float(v) for v in p.astype(np.float32)]
+        out.append(c)
+    return out
+
+
+_CAMERA_KEYS = {"position": 3, "look": 3, "up": 3, "vfov_deg": 1}
+
+
+def read_camera_path(path) -> list:
+    """A camera path: a JSON list of {"position": [x, y, z], "look": [x, y, z], "up"?: [x, y, z], "vfov_deg"?: v}, one
+    per frame -> a list of dicts of floats (what Integrator.set_camera takes as keywords; an absent optional key keeps
+    the scene's value).  Strict like read_configuration: an unknown key, a missing position or look, a wrong length
+    or a non-number is a ValueError."""
+    import json
+
+    with open(path, "r", encoding="utf-8") as f:
+        data = json.load(f)
+    if not isinstance(data, list) or not data:
+        raise ValueError(f"{path}: a camera path is a non-empty JSON list of cameras")
+    out = []
+    for i, cam in enumerate(data):
+        if not isinstance(cam, dict):
+            raise ValueError(f"{path}: frame {i}: a camera is an object")
+        for k in cam:
+            if k not in _CAMERA_KEYS:
+                raise ValueError(f"{path}: frame {i}: unknown key {k!r}")
+        for k in ("position", "look"):
+            if k not in cam:
+                raise ValueError(f"{path}: frame {i}: missing key {k!r}")
+        d = {}
+        for k, v in cam.items():
+            vals = v if _CAMERA_KEYS[k] == 3 else [v]
+            if (not isinstance(vals, list) or len(vals) != _CAMERA_KEYS[k]
+                    or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in vals)):
+                raise ValueError(f"{path}: frame {i}: {k!r} wants {_CAMERA_KEYS[k]} number(s)")
+            d[k] = [float(x) for x in vals] if _CAMERA_KEYS[k] == 3 else float(v)
+        out.append(d)
+    return out
+
+
+def with_camera(cfg: capi.Configuration, position=None, look=None, up=None, vfov_deg=None) -> capi.Configuration:
+    """A copy of cfg with the camera fields given replaced (a read_camera_path entry as keywords)."""
+    c = cfg.copy()
+    cp = c.camera_parameters
+    for name, v in (("position", position), ("look", look), ("up", up)):
+        if v is not None:
+            getattr(cp, name)[:] = [float(x) for x in v]
+    if vfov_deg is not None:
+        cp.vfov_deg = float(vfov_deg)
+    return c
+
+
 def _standin_camera(cfg: capi.Configuration, distance: float) -> None:
     cp = cfg.camera_parameters
     cp.position[:] = [0.0, 0.0, -float(distance)]
