@@ -131,3 +131,86 @@ def temperature_pair(kind):
         return dens, remapped(SynthGrid(2, 128).grid(copy=True), 0.5 * np.eye(3), (0.0, 0.0, 0.0))
     raise ValueError(kind)
 
+
+
+# ---- grids shaped like a real .nvdb: a background, leaves across node boundaries, far index coordinates, boxes that
+# cut leaves or reach into empty root space, inactive voxels with values, denormal values (tests/grid_cases.py) ------
+def _rebuilt(base: capi.Grid, **kw) -> capi.Grid:
+    """`base` with the given constructor arguments replaced; arrays not replaced are copied."""
+    d = base.desc
+    args = dict(map_mat=list(d.map_mat), map_inv_mat=list(d.map_inv_mat), map_vec=list(d.map_vec),
+                background=float(d.background), bbox_min=list(d.index_bbox_min), bbox_max=list(d.index_bbox_max),
+                leaf_origin=base.leaf_origin.copy(), leaf_values=base.leaf_values.copy(), leaf_max=base.leaf_max.copy(),
+                leaf_value_mask=base.leaf_value_mask.copy())
+    if base.tile_origin is not None:
+        args.update(tile_origin=base.tile_origin.copy(), tile_level=base.tile_level.copy(),
+                    tile_value=base.tile_value.copy(), tile_active=base.tile_active.copy())
+    args.update(kw)
+    return capi.Grid(**args)
+
+
+def moved(base: capi.Grid, shift, background=None, pad_lo=(0, 0, 0), pad_hi=(0, 0, 0), tiles=None) -> capi.Grid:
+    """The same voxels at index coordinates + shift (multiples of 8 per axis), with map_vec - M @ shift: the world
+    space scene, and so an unchanged camera, sees the same volume.  background: another background value;
+    pad_lo / pad_hi: the index box grown by that many voxels below / above; tiles: dict(tile_origin=, tile_level=,
+    tile_value=, tile_active=) at final index coordinates, replacing the base's tiles (which otherwise move along)."""
+    shift = np.broadcast_to(np.asarray(shift, np.int64), (3,))
+    assert (shift % 8 == 0).all()
+    d = base.desc
+    m = np.asarray(d.map_mat[:], np.float64).reshape(3, 3)
+    vec = np.asarray(d.map_vec[:], np.float64) - m @ shift.astype(np.float64)
+    kw = dict(map_vec=vec.astype(np.float32),
+              leaf_origin=(base.leaf_origin.astype(np.int64) + shift).astype(np.int32),
+              bbox_min=(np.asarray(d.index_bbox_min[:], np.int64) + shift - np.asarray(pad_lo, np.int64)).tolist(),
+              bbox_max=(np.asarray(d.index_bbox_max[:], np.int64) + shift + np.asarray(pad_hi, np.int64)).tolist())
+    if background is not None:
+        kw["background"] = background
+    if tiles is not None:
+        kw.update(tiles)
+    elif base.tile_origin is not None:
+        kw["tile_origin"] = (base.tile_origin.astype(np.int64) + shift).astype(np.int32)
+    return _rebuilt(base, **kw)
+
+
+def leaves_where(base: capi.Grid, keep) -> capi.Grid:
+    """The leaves selected by the bool mask `keep` under the base's map, box, background and tiles: a volume cut
+    through its middle, so dense voxels lie on the cut."""
+    keep = np.asarray(keep, bool)
+    return _rebuilt(base, leaf_origin=base.leaf_origin[keep], leaf_values=base.leaf_values[keep],
+                    leaf_max=base.leaf_max[keep], leaf_value_mask=base.leaf_value_mask[keep])
+
+
+def with_background(base: capi.Grid, value) -> capi.Grid:
+    """The same leaves under another background value."""
+    return _rebuilt(base, background=value)
+
+
+def with_bbox(base: capi.Grid, lo, hi) -> capi.Grid:
+    """The same leaves under another index bounding box [lo, hi] (inclusive, as NanoVDB's)."""
+    return _rebuilt(base, bbox_min=[int(v) for v in lo], bbox_max=[int(v) for v in hi])
+
+
+def inactive_half(base: capi.Grid) -> capi.Grid:
+    """The same values with every second word of leaf_value_mask cleared: inactive voxels that hold values (a
+    lookup returns a voxel's value whatever its active bit)."""
+    mask = base.leaf_value_mask.copy()
+    mask[:, 1::2] = 0
+    return _rebuilt(base, leaf_value_mask=mask)
+
+
+def denormal_slab(base: capi.Grid, bits: int) -> capi.Grid:
+    """In the leaves with origin.x < 32 every voxel v becomes the float32 whose bit pattern is
+    floor(v / leafmax * bits) (leafmax: the leaf's largest value), so with bits <= 0x7fffff the slab holds zeros and
+    denormals only, its leaf maxima the pattern `bits`; leaf_max is recomputed.  Two active lower-node tiles at
+    (64, 0, 0) and (64, 8, 0) hold the bit patterns 17 and 64: inside and just outside the range of patterns the
+    walk table reads as zero-run radii (1 .. 63).  The index box stays the base's, so the tiles lie outside it: the
+    table builders read them (walk words, cells8, the dense pool's bricks), rays do not."""
+    values = base.leaf_values.copy()
+    slab = base.leaf_origin[:, 0] < 32
+    v = values[slab].astype(np.float64)
+    top = v.max(axis=1, keepdims=True)
+    pattern = np.floor(v / np.where(top > 0, top, 1.0) * float(bits))
+    values[slab] = pattern.astype(np.uint32).view(np.float32)
+    vmax = values.max(axis=1).astype(np.float32)
+    return _rebuilt(base, leaf_values=values, leaf_max=vmax, tile_origin=[[64, 0, 0], [64, 8, 0]], tile_level=[1, 1],
+                    tile_value=np.array([17, 64], np.uint32).view(np.float32), tile_active=[1, 1])

@@ -1201,8 +1201,11 @@ __global__ void vpt_majorant_trace_kernel(const DevScene* scene, float ox, float
   if (begin_ray(G, ln, o, ray_dir_setup(G, d))) {
     while (ln.s_t1 < ln.T1) {  // RayMajorantIterator::next: segments until the HDDA leaves [t0, t1]
       begin_segment(ln);
-      while (!hdda_step(G, ln)) {
-      }
+      // volume.cpp:54 assigns d_maj in every iteration of the do-while, so of cells whose majorants compare equal
+      // without being the same bits (+0 and -0) the segment reports the last one's, not the first's.  (The
+      // integrator only ever tests d_maj <= 0 there, so begin_segment's copy serves it.)
+      float d_maj = ln.s_dmaj;
+      while (!hdda_step(G, ln)) d_maj = ln.maj;
       if (n < max_rows) {
         const float w0 = ln.s_t0 * ln.scale, w1 = ln.s_t1 * ln.scale;  // t * idx_to_world_scale()
         float p0[3], p1[3], q0[3], q1[3];
@@ -1219,7 +1222,7 @@ __global__ void vpt_majorant_trace_kernel(const DevScene* scene, float ox, float
         }
         row[6] = w0;
         row[7] = w1;
-        row[8] = ln.s_dmaj;
+        row[8] = d_maj;
       }
       ++n;
     }
