@@ -386,6 +386,43 @@ int vpt_gpu_render_tiles(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t tile_hi, u
  * the film.  Feeds are unaffected and never write the plane.  Takes effect at the next launch. */
 int vpt_gpu_set_film_moments(vpt_gpu_ctx* ctx, float* m2_device);
 
+/* Light groups.  The radiance is linear in the reference's three sources -- blackbody emission at collisions
+ * (worker.cpp:156), the distant light through sample_Ld (:175), the infinite light on escape (:199) -- and no random
+ * draw depends on their strength (apart from sample_Ld's test Li == 0), so one set of paths holds every relit
+ * picture once the three sums are kept apart.
+ *
+ * `groups_device` is a device float[3][H][W][4] owned by the caller (16-byte aligned), in the order emission, sun,
+ * sky; each plane is an ordinary XYZW film.  NULL detaches.  The contract is vpt_gpu_set_film_moments': while
+ * attached every ordered production launch (vpt_gpu_render_jobs, vpt_gpu_render_tiles, vpt_gpu_render_tile_list,
+ * the launches they are split into under max_bytes included) keeps, beside each sample's L, one fp32 accumulator per
+ * group that receives only that group's adds, in path order and not contracted,
+ *     emission:  E = E + (p_a * le_scale) * XYZ           at every collision (worker.cpp:156)
+ *     sun:       D = D + (p * T_ray) * Li                  or D + 0.0f when sample_Ld returned zero (:175)
+ *     sky:       le_inf if the path escaped, else +0.0     (:199)
+ * and after the film's four adds, in the same wave order, does for each group g
+ *     G[g].w = G[g].w + 1;   G[g].xyz = G[g].xyz + imaging_ratio * Lg.xyz       (fp32, not contracted).
+ * A scene without a temperature grid adds +0.0 samples to the emission plane.  Each plane is therefore, bit for bit
+ * (up to the sign of a zero), the film the reference renders with the other two sources switched off.  The beauty
+ * film is unchanged; it is NOT the sum of the planes bit for bit (fp32 addition does not associate), only to a few
+ * ulp.  Pixels that receive no sample are not touched.  The moment plane and the groups combine.
+ * Memory: the sample buffer of a launch holds 48 bytes per sample instead of 12 (the sample, then its three group
+ * terms, 12 bytes each, in four regions of the same layout); max_bytes splits launches accordingly and
+ * vpt_gpu_film_order_info reports the buffer.  Launches with groups run the throughput kernels.
+ * VPT_E_STATE with VPT_FILM_ATOMIC and while a frame is open.  With groups attached a launch that would add with
+ * film atomics -- a debug launch (records, events), the pixel RNG mode, VPT_FILM_ATOMIC, an open frame, a sample
+ * buffer that would have to grow while a feed of the context is open -- and vpt_gpu_render_adaptive_fused fail with
+ * VPT_E_STATE instead of leaving the planes behind the film.  Feeds are unaffected and never write the planes.  The
+ * attachment survives vpt_gpu_set_scene and vpt_gpu_set_grids.  Takes effect at the next launch. */
+int vpt_gpu_set_light_groups(vpt_gpu_ctx* ctx, float* groups_device);
+
+/* Relights group planes: for each pixel of the context's W x H frame
+ *     out.c = ((G0.c * k0.c) + (G1.c * k1.c)) + (G2.c * k2.c)   for c = X, Y, Z;     out.w = G0.w
+ * in fp32, in this order, not contracted.  `groups_device`: float[3][H][W][4] as above; `gains`: host, row-major
+ * [group][XYZ]; `film_out_device`: float[H][W][4], which must not overlap the planes (VPT_E_INVALID).  Both 16-byte
+ * aligned.  One small kernel on `hip_stream`; the call does not wait for it. */
+int vpt_gpu_relight(vpt_gpu_ctx* ctx, const float* groups_device, const float gains[9], float* film_out_device,
+                    void* hip_stream);
+
 /* A tile-list launch: vpt_gpu_render_tiles for the tiles tiles[0..n) (a host array, strictly ascending, every entry
  * < T) instead of [tile_lo, tile_hi): renders the jobs (wave_begin + w) * T + tiles[i], w in [0, wave_count), adds
  * each pixel's samples in wave order and touches no pixel outside the listed tiles.  Order: the list's tiles by

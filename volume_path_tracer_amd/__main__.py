@@ -27,6 +27,15 @@ camera per frame ({position, look, up?, vfov_deg?}), ``--volume-sequence PATTERN
 ``PATTERN % k`` in frame k (read while frame k - 1 is written).  Every output path given must then hold exactly one
 ``%d``-style field for the frame index; each frame runs the single frame's code path with the same flags, its files are
 written on a second thread while the next frame renders, and a closing line reports the update time and the total.
+``--light-groups`` renders with light-group planes attached (Integrator.set_light_groups: the emission, the distant
+light and the infinite light each in a film of its own, from the one set of paths) and writes ``<out>.emission.png``,
+``<out>.sun.png`` and ``<out>.sky.png`` next to the beauty PNG, whose bytes do not change; the uniform frame is then
+one ordered launch (render.render_uniform), the adaptive one the rounds driver.  ``--groups-out g.npy`` saves the planes
+(float32 [3][H][W][4]).  ``--relight emission=K,sun=K,sky=K`` (implies ``--light-groups``; each K one number or X:Y:Z,
+an absent group keeps 1) writes the output PNG from the relit film (Integrator.relight) instead; ``--film-out`` still
+saves the raw film.  ``--relight-from g.npy`` relights a saved file with the same arithmetic in numpy (image.relight)
+and opens no device: the configuration is not read.  Not with ``--denoise``, ``--alpha-foreground`` or
+``--adaptive-fused``.
 Exits 1 on a fatal error, like vptFATAL.
 """
 from __future__ import annotations
@@ -47,6 +56,27 @@ def _parse_synth(spec: str):
 
 
 _FIELD = re.compile(r"%0?\d*d")
+_GROUPS = ("emission", "sun", "sky")
+
+
+def _parse_relight(spec: str):
+    """--relight's gains: 'emission=K,sun=K,sky=K', each K a number or X:Y:Z -> 3 x 3 floats [group][XYZ]."""
+    k = [[1.0, 1.0, 1.0] for _ in _GROUPS]
+    for part in filter(None, (spec or "").split(",")):
+        name, eq, val = part.partition("=")
+        if not eq or name.strip() not in _GROUPS:
+            raise ValueError(f"--relight wants emission=K,sun=K,sky=K (K a number or X:Y:Z), got {part!r}")
+        v = [float(x) for x in val.split(":")]
+        if len(v) not in (1, 3):
+            raise ValueError(f"--relight {name}: one number or X:Y:Z, got {val!r}")
+        k[_GROUPS.index(name.strip())] = v * 3 if len(v) == 1 else v
+    return k
+
+
+def _group_path(output_path: str, name: str) -> str:
+    """<out>.<group>.png next to the beauty PNG <out>.png."""
+    stem = output_path[:-4] if output_path.lower().endswith(".png") else output_path
+    return f"{stem}.{name}.png"
 
 
 def _frame_path(pattern: str, k: int) -> str:
@@ -116,15 +146,46 @@ def main(argv=None) -> int:
                     help="sequence: one camera per frame, a JSON list of {position, look, up?, vfov_deg?}")
     ap.add_argument("--volume-sequence", default=None, metavar="PATTERN",
                     help="sequence: frame k renders the volume file PATTERN %% k (.nvdb or .npz), swapped in place")
+    ap.add_argument("--light-groups", action="store_true",
+                    help="also write <out>.emission.png, <out>.sun.png, <out>.sky.png: one film per light source")
+    ap.add_argument("--groups-out", default=None, help="light groups: save the planes (.npy, float32 [3][H][W][4])")
+    ap.add_argument("--relight", default=None, metavar="emission=K,sun=K,sky=K",
+                    help="implies --light-groups: the output PNG from the relit film; K a number or X:Y:Z")
+    ap.add_argument("--relight-from", default=None, metavar="G.npy",
+                    help="relight saved planes (--groups-out) into output_path; opens no device")
     args = ap.parse_args(argv)
     if (args.denoised_film_out or args.moments_out) and not args.denoise:
         ap.error("--denoised-film-out and --moments-out need --denoise")
+    want_groups = bool(args.light_groups or args.groups_out or args.relight is not None)
+    try:
+        gains = _parse_relight(args.relight)
+    except ValueError as e:
+        print(f"[vpt] FATAL: {e}", file=sys.stderr)
+        return 1
+    if want_groups or args.relight_from:
+        for flag, on in (("--denoise", args.denoise), ("--alpha-foreground", args.alpha_foreground),
+                         ("--adaptive-fused", args.adaptive_fused)):
+            if on:
+                print(f"[vpt] FATAL: {flag} does not combine with --light-groups / --relight (out of scope: README, "
+                      f"Light groups)", file=sys.stderr)
+                return 1
+    if args.relight_from:  # host work only: no device, no configuration
+        try:
+            import numpy as np
+
+            from . import image
+
+            image.save_png(args.output_path, image.film_to_image(image.relight(np.load(args.relight_from), gains)))
+        except Exception as e:
+            print(f"[vpt] FATAL: {e}", file=sys.stderr)
+            return 1
+        return 0
 
     # ---- sequences: every output path is a pattern over the frame index (checked before anything touches a device)
     sequence = args.frames is not None or args.camera_path is not None or args.volume_sequence is not None
     outputs = {"output_path": args.output_path, "--film-out": args.film_out, "--alpha-out": args.alpha_out,
                "--waves-out": args.waves_out, "--denoised-film-out": args.denoised_film_out,
-               "--moments-out": args.moments_out, "--event-log": args.event_log}
+               "--moments-out": args.moments_out, "--event-log": args.event_log, "--groups-out": args.groups_out}
     if sequence:
         problem = _sequence_problem(args, outputs)
         if problem:
@@ -153,7 +214,10 @@ def main(argv=None) -> int:
         if args.adaptive is not None:
             film, waves, err, info, *plane = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
                                                              step_waves=args.spp_step, max_waves=cfg.num_waves,
-                                                             fused=args.adaptive_fused, return_moments=args.denoise)
+                                                             fused=args.adaptive_fused, return_moments=args.denoise,
+                                                             groups=want_groups)
+            if want_groups:
+                res["groups"] = plane.pop()
             m2 = plane[0] if plane else None
             ms = (time.perf_counter() - t0) * 1e3
             driver = "one launch (fused)" if args.adaptive_fused else "rounds"
@@ -169,6 +233,11 @@ def main(argv=None) -> int:
             ms = (time.perf_counter() - t0) * 1e3
             print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
                   file=sys.stderr)
+        elif want_groups:  # the ordered frame with its group planes (the feed writes none)
+            film, res["groups"] = (t.cpu().numpy() for t in render_uniform(it, moments=False, groups=True))
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp, light groups)",
+                  file=sys.stderr)
         else:
             tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
             tp.reset_eta()
@@ -182,6 +251,10 @@ def main(argv=None) -> int:
             emit("events")
         res["film"] = film
         emit("film")
+        if want_groups:
+            emit("groups")
+            if args.relight is not None:
+                res["relit"] = it.relight(res["groups"], gains)
         if args.alpha or args.alpha_foreground or args.alpha_out:
             if args.denoise and not args.denoise_no_guides:  # one pass serves the matte and the guides
                 guides = matte_guides(it, sub=args.alpha_sub or 1)
@@ -206,7 +279,7 @@ def main(argv=None) -> int:
         emit("png")
         return res
 
-    PIECES = ("waves", "events", "film", "alpha", "m2", "denoised", "png")
+    PIECES = ("waves", "events", "film", "groups", "alpha", "m2", "denoised", "png")
 
     def write_piece(piece, res, paths):
         """One of a frame's files, from what render_frame has produced (host work only)."""
@@ -218,6 +291,11 @@ def main(argv=None) -> int:
             traces.write_event_log(res["events"], paths["--event-log"])
         elif piece == "film" and paths["--film-out"]:
             np.save(paths["--film-out"], res["film"])
+        elif piece == "groups" and "groups" in res:
+            if paths["--groups-out"]:
+                np.save(paths["--groups-out"], res["groups"])
+            for name, plane in zip(_GROUPS, res["groups"]):
+                image.save_png(_group_path(paths["output_path"], name), image.film_to_image(plane))
         elif piece == "alpha" and "alpha" in res and paths["--alpha-out"]:
             np.save(paths["--alpha-out"], res["alpha"])
         elif piece == "m2" and args.denoise and paths["--moments-out"]:
@@ -225,7 +303,7 @@ def main(argv=None) -> int:
         elif piece == "denoised" and args.denoise and paths["--denoised-film-out"]:
             np.save(paths["--denoised-film-out"], res["denoised"])
         elif piece == "png":
-            film = res["denoised"] if args.denoise else res["film"]
+            film = res["denoised"] if args.denoise else res.get("relit", res["film"])
             if args.alpha or args.alpha_foreground:
                 alpha = res["alpha"]
                 rgb = image.film_to_image(image.foreground_film(film, alpha, res["cfg"]) if args.alpha_foreground else film)

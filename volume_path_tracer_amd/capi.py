@@ -291,6 +291,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "vpt_gpu_render_adaptive_fused"):
         L.vpt_gpu_render_adaptive_fused.argtypes = [vp, C.POINTER(AdaptiveParams), vp, vp, C.POINTER(C.c_uint32), fp,
                                                     C.POINTER(AdaptiveResult), vp]
+    if hasattr(L, "vpt_gpu_set_light_groups"):  # (older builds in A/B runs lack the light groups)
+        L.vpt_gpu_set_light_groups.argtypes = [vp, vp]
+        L.vpt_gpu_relight.argtypes = [vp, vp, fp, vp, vp]
     if hasattr(L, "vpt_gpu_render_alpha"):  # (older builds in A/B runs lack the coverage pass)
         L.vpt_gpu_render_alpha.argtypes = [vp, C.c_uint32, vp, vp, vp]
     if hasattr(L, "vpt_gpu_denoise"):  # (older builds in A/B runs lack the denoiser)

@@ -168,6 +168,9 @@ struct vpt_gpu_ctx {
   // passes while attached.  tile_err: vpt_gpu_tile_errors' T results (device, allocated with band_rank).
   float* m2 = nullptr;
   float* tile_err = nullptr;
+  // The light-group planes (vpt_gpu_set_light_groups): the caller's float[3][H][W][4] (emission, sun, sky), written
+  // by the ordered film passes while attached.
+  float* groups = nullptr;
   // Gang launches (vpt_gpu_render_adaptive_fused): the wavefronts' sample scratch (wavefronts x tile_area x 64 x 3
   // floats, grown when the grid does) and the tiles' wave counts (T words; their errors go to tile_err).  Allocated
   // by the first call, freed with the context.

@@ -468,7 +468,9 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // The ordered film: production launches of the reference RNG mode (debug launches and feeds add atomically).
   // A launch whose sample buffer would exceed the cap is rendered as consecutive launches (whole waves where it
   // can); each adds its own waves in order, so the film is the same.
-  const uint64_t per_job = (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
+  // Light groups (vpt_gpu_set_light_groups): four regions of the sample layout instead of one (kGroupRegions).
+  const bool groups = ctx->groups != nullptr && !feed;
+  const uint64_t per_job = (uint64_t)ctx->scene.tile_area * 3 * sizeof(float) * (groups ? vpt::kGroupRegions : 1);
   const bool ordered = ctx->film_order == VPT_FILM_ORDERED && !feed && !records && !events && !ctx->scene.pixel_mode;
   // The moment plane (vpt_gpu_set_film_moments) is written by the ordered film passes only: a launch that would add
   // with film atomics fails instead of leaving the plane behind the film.  (Feeds never write it.)
@@ -478,6 +480,13 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
                                                        : records || events ? "a debug launch"
                                                                            : "not an ordered launch of the reference RNG mode") +
                                            "): detach it (vpt_gpu_set_film_moments NULL)");
+  // The light-group planes likewise: written by the ordered film passes only.
+  if (groups && (!ordered || ctx->frame_waves))
+    return vpt::set_error(VPT_E_STATE, "render: light groups are attached and this launch would add with film atomics (" +
+                                           std::string(ctx->frame_waves ? "a frame is open"
+                                                       : records || events ? "a debug launch"
+                                                                           : "not an ordered launch of the reference RNG mode") +
+                                           "): detach them (vpt_gpu_set_light_groups NULL)");
   if (ordered && !band) {  // (vpt_gpu_render_tiles splits its launches itself: by waves)
     const uint64_t max_jobs = std::min<uint64_t>(ordered_cap(ctx, jid_count * per_job) / per_job, 0xffffffffULL);
     if (max_jobs == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one job's samples");
@@ -563,7 +572,8 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // wave instructions to launches that are issue-bound; r04k, profiles/archive/r04k_lat_gated_ab.txt).  lat_mode 1
   // forces it.  Same jobs, same samples.
   const uint64_t lat_blocks = cus * (uint64_t)ctx->lat_per_cu;
-  const bool use_lat = !dbg && !feed && ctx->lat_mode != 0 &&
+  // (a launch with light groups always takes the throughput kernel: samples do not depend on the kernel)
+  const bool use_lat = !dbg && !feed && !groups && ctx->lat_mode != 0 &&
                        (ctx->lat_mode == 1 || (!ctx->grid_user && (latency || blocks <= lat_blocks)));
   if (use_lat) blocks = (uint32_t)std::min<uint64_t>(latency ? lat_blocks : blocks, lat_blocks);
   // Live-path compaction (vpt_gpu_set_compaction): partly filled launches of the latency kernel whose grid fits
@@ -603,7 +613,8 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   float* samples = nullptr;
   // (while the drop-in's ordered frame is open its feeds own the sample buffer: other launches add with atomics)
   if (band) {
-    const uint64_t bytes = vpt::band_sample_floats(band->tiles, band->waves, ctx->scene.tile_area, band->group) * sizeof(float);
+    const uint64_t bytes = vpt::band_sample_floats(band->tiles, band->waves, ctx->scene.tile_area, band->group) * sizeof(float) *
+                           (groups ? vpt::kGroupRegions : 1);
     if ((rc = ensure_samples(ctx, bytes, samples))) return rc;
     if (!samples)
       return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tiles: the sample buffer would have to grow (" +
@@ -614,7 +625,12 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   if (ctx->m2 && !feed && !samples)
     return vpt::set_error(VPT_E_STATE, "render: a moment plane is attached and the sample buffer would have to grow while "
                                        "a feed of the context is open (the launch would add with film atomics)");
+  if (groups && !samples)
+    return vpt::set_error(VPT_E_STATE, "render: light groups are attached and the sample buffer would have to grow while "
+                                       "a feed of the context is open (the launch would add with film atomics)");
   env.samples = samples;
+  env.group_stride = band ? vpt::band_sample_floats(band->tiles, band->waves, ctx->scene.tile_area, band->group)
+                          : jid_count * (uint64_t)ctx->scene.tile_area * 3;
   if (samples) {
     ++ctx->ordered_launches;
     if (ctx->samples_used) VPT_HIP(hipStreamWaitEvent(s, ctx->samples_done, 0));  // the buffer's previous launch
@@ -684,7 +700,18 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // first slots would leave the fetching slots to finished ones)
   const vpt::DevScene* scene =
       latency || (use_lat && ctx->lat_ungated && !compact) ? ctx->scene_lat_dev : ctx->scene_dev;
-  if (band) {  // the Band instantiations of the same kernels, by the same rules
+  if (groups) {  // the Groups instantiations of the throughput kernels, plain or band (never a debug launch)
+    auto kernel = band ? (temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, true, false, true>
+                          : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, true, false, true>
+                                          : vpt::vpt_integrate_kernel<false, false, false, false, false, false, true, false, true>)
+                       : (temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, false, false, true>
+                          : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, false, false, true>
+                                          : vpt::vpt_integrate_kernel<false, false, false, false, false, false, false, false, true>);
+    if (scene == ctx->scene_dev) scene = ctx->scene_full_dev;  // (the full-launch gates, as below)
+    // no temperature grid: no emission.  The kernel leaves region 1 alone; the pass below adds its +0.0 samples.
+    if (!temp) VPT_HIP(hipMemsetAsync(samples + env.group_stride, 0, env.group_stride * sizeof(float), s));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
+  } else if (band) {  // the Band instantiations of the same kernels, by the same rules
     if (use_lat) {
       env.compact_every = (uint32_t)std::max(1, ctx->compact_every);
       if (compact) {
@@ -746,6 +773,13 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
                        dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev, env.film, (const float*)samples,
                        band->tile_lo, band->waves, env.band_groups, band->group, list, ctx->m2);
     VPT_HIP(hipGetLastError());
+    // the group planes: the same pass over each group's region (w += 1, xyz += imaging_ratio * Lg, in wave order)
+    for (uint64_t g = 0; groups && g < 3; ++g) {
+      hipLaunchKernelGGL(vpt::vpt_band_order_kernel<false>, dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev,
+                         ctx->groups + g * npix * 4, (const float*)samples + (g + 1) * env.group_stride, band->tile_lo,
+                         band->waves, env.band_groups, band->group, list, (float*)nullptr);
+      VPT_HIP(hipGetLastError());
+    }
     VPT_HIP(hipEventRecord(ctx->samples_done, s));
     ctx->samples_used = true;
   } else if (samples) {  // the film, pixel by pixel in wave order (sample counts included)
@@ -754,6 +788,12 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
                        dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ctx->scene_dev, env.film,
                        (const float*)samples, jid_begin, jid_count, ctx->m2);
     VPT_HIP(hipGetLastError());
+    for (uint64_t g = 0; groups && g < 3; ++g) {  // the group planes, as above
+      hipLaunchKernelGGL(vpt::vpt_film_order_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
+                         ctx->scene_dev, ctx->groups + g * npix * 4, (const float*)samples + (g + 1) * env.group_stride,
+                         jid_begin, jid_count, (float*)nullptr);
+      VPT_HIP(hipGetLastError());
+    }
     VPT_HIP(hipEventRecord(ctx->samples_done, s));
     ctx->samples_used = true;
   } else if (!feed) {  // a feed adds its sample counts when it is closed (vpt_tile_count_kernel)
@@ -1003,7 +1043,8 @@ int check_device(int device, const char* what) {
 int render_band_waves(vpt_gpu_ctx* ctx, uint32_t tile_lo, uint32_t B, bool list, uint64_t wave_begin, uint64_t wave_count,
                       float* film_device, void* hip_stream) {
   const uint64_t T = ctx->scene.T, G = vpt::kBandGroup;
-  const uint64_t per_wave = (uint64_t)B * (uint64_t)ctx->scene.tile_area * 3 * sizeof(float);
+  const uint64_t per_wave = (uint64_t)B * (uint64_t)ctx->scene.tile_area * 3 * sizeof(float) *
+                            (ctx->groups ? vpt::kGroupRegions : 1);
   const uint64_t max_waves = ordered_cap(ctx, (wave_count + G - 1) / G * G * per_wave) / per_wave;
   if (max_waves == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one wave of the band's samples");
   const uint64_t chunk = max_waves >= G ? max_waves / G * G : max_waves;
@@ -1399,6 +1440,38 @@ int vpt_gpu_set_film_moments(vpt_gpu_ctx* ctx, float* m2_device) {
   return VPT_OK;
 }
 
+int vpt_gpu_set_light_groups(vpt_gpu_ctx* ctx, float* groups_device) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_light_groups: null context");
+  if (groups_device && (uintptr_t)groups_device % 16 != 0)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_light_groups: the planes must be 16-byte aligned");
+  if (groups_device && ctx->film_order != VPT_FILM_ORDERED)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_light_groups: the planes are written by the ordered film passes "
+                                       "(vpt_gpu_set_film_order: VPT_FILM_ORDERED)");
+  if (groups_device && ctx->frame_waves)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_light_groups: a frame is open (its launches add with film atomics)");
+  ctx->groups = groups_device;  // read by the next render's host code only: no wait
+  return VPT_OK;
+}
+
+int vpt_gpu_relight(vpt_gpu_ctx* ctx, const float* groups_device, const float gains[9], float* film_out_device,
+                    void* hip_stream) {
+  if (!ctx || !groups_device || !gains || !film_out_device)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_relight: null argument");
+  if (((uintptr_t)groups_device | (uintptr_t)film_out_device) % 16 != 0)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_relight: the planes must be 16-byte aligned");
+  const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
+  if (ranges_overlap(film_out_device, npix * 16, groups_device, 3 * npix * 16))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_relight: the output aliases the group planes");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  vpt::RelightGains K;
+  for (int i = 0; i < 9; ++i) K.k[i] = gains[i];
+  hipLaunchKernelGGL(vpt::vpt_relight_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream,
+                     reinterpret_cast<const float4*>(groups_device), K, npix, reinterpret_cast<float4*>(film_out_device));
+  VPT_HIP(hipGetLastError());
+  return VPT_OK;
+}
+
 int vpt_gpu_tile_errors(vpt_gpu_ctx* ctx, const float* film_device, const float* m2_device, float abs_floor,
                         float* err_T_host, void* hip_stream) {
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_tile_errors: null context");
@@ -1490,6 +1563,9 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
                                          ">= min_waves, target_error >= 0 and abs_floor > 0");
   int rc = ctx_device(ctx);
   if (rc) return rc;
+  if (ctx->groups)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: light groups are attached and gang launches do not "
+                                       "write them: detach them (vpt_gpu_set_light_groups NULL) or use vpt_gpu_render_adaptive");
   if (ctx->scene.pixel_mode)
     return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_adaptive_fused: gang launches run the reference RNG mode");
   if (ctx->scene.tile_area > vpt::kGangMaxArea)

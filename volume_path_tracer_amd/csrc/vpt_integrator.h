@@ -1016,6 +1016,21 @@ __host__ __device__ inline void scene_finalize(DevScene& S) {
   S.sigt_c = S.sigma_t * kOvershootC;
 }
 
+// Env::kGroups, false for an environment without one: light groups (vpt_gpu_set_light_groups).  Besides L the lane
+// keeps one fp32 accumulator per light source next to it in the cold state, each fed only its own adds, in path order:
+// the emission's sc * XYZ (group_emit; HasTemp only), the distant light's pt * Li or + 0.0f (group_sun /
+// group_sun_zero); group_begin zeroes them where L is zeroed.  The infinite light's term needs no accumulator: it is
+// le_inf iff the path ends in ST_FINISH, which film_add still reads in the lane's state.  L itself is untouched, so
+// the beauty sample stays the reference's bit for bit; the sum of the groups is not (fp32 association).
+template <class Env, class = void>
+struct env_groups {
+  static constexpr bool value = false;
+};
+template <class Env>
+struct env_groups<Env, decltype((void)Env::kGroups)> {
+  static constexpr bool value = Env::kGroups;
+};
+
 // A primary ray's real-or-null collision (worker.cpp:148-188) at the index point pi with density
 // dens: emission (HasTemp), then sample_discrete({Null, Absorption, Scatter}, u) with
 // p_a = sigma_a*dens/sigma_maj, p_s = sigma_s*dens/sigma_maj.  u < 0: draw the event's uniform here
@@ -1049,6 +1064,7 @@ __host__ __device__ __forceinline__ void primary_event(ScenePtr sp, const DevSce
     lc.L[0] = lc.L[0] + sc * X;
     lc.L[1] = lc.L[1] + sc * Y;
     lc.L[2] = lc.L[2] + sc * Z;
+    if constexpr (env_groups<Env>::value) env.group_emit(sc, X, Y, Z);
   }
   if (u < 0.0f) {
     u = rng_uniform(ln.rng);
@@ -1360,12 +1376,14 @@ __host__ __device__ __forceinline__ void nee_done(const DevScene& S, Lane& ln, L
     lc.L[0] = lc.L[0] + pt * S.Li[0];
     lc.L[1] = lc.L[1] + pt * S.Li[1];
     lc.L[2] = lc.L[2] + pt * S.Li[2];
+    if constexpr (env_groups<Env>::value) env.group_sun(pt, S.Li[0], S.Li[1], S.Li[2]);
   } else {
     // L + 0.0f (sample_Ld returned zero): the same value as L for every L but -0.0, which it
     // turns into +0.0 -- written as a select, so no register holds a constant for it.
     lc.L[0] = lc.L[0] == 0.0f ? 0.0f : lc.L[0];
     lc.L[1] = lc.L[1] == 0.0f ? 0.0f : lc.L[1];
     lc.L[2] = lc.L[2] == 0.0f ? 0.0f : lc.L[2];
+    if constexpr (env_groups<Env>::value) env.group_sun_zero();
   }
   float u0 = rng_uniform(ln.rng);
   float u1 = rng_uniform(ln.rng);
@@ -1616,6 +1634,7 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
         lc.rd[i] = dv[i];
         lc.L[i] = 0.0f;
       }
+      if constexpr (env_groups<Env>::value) env.group_begin();
       lc.depth = 0;
       ln.shadow = 0;
       ln.state = ST_RAY;

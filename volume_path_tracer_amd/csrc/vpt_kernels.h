@@ -112,6 +112,11 @@ struct KernelArgs {
   float* gang_err;
   float gang_target, gang_floor;
   uint32_t gang_min, gang_step, gang_max;
+  // Light groups (vpt_gpu_set_light_groups; the kernels' Groups instantiations only): the sample buffer holds four
+  // regions of the launch's sample layout (plain or band), group_stride floats apart -- the beauty samples, then each
+  // sample's emission, sun and sky terms at the same offset in regions 1, 2, 3 (a launch without a temperature grid
+  // leaves region 1 to the host, which zeroes it).  The film passes then run once per region.
+  uint64_t group_stride;
 };
 typedef const __attribute__((address_space(4))) KernelArgs* ArgsPtr;
 // This workgroup's event counters and (VPT_PROFILE builds) section cycles; the temperature kernel's LDS copy of
@@ -123,6 +128,11 @@ __shared__ unsigned long long g_wg_prof[PT_COUNT + kBlockThreads / 64];
 __shared__ float g_bb_lds[kBbFloats];
 // A finish-block pass's samples, per wavefront by rank: (pixel index << 6) | lane (KernelEnvT::film_add / film_commit).
 __shared__ uint32_t g_film_rank[kBlockThreads];
+// Light groups (KernelEnvT<.., Groups>): the lane's per-source accumulators beside LaneCold::L, [component][thread] so a
+// wavefront's accesses hit 64 different banks.  A kernel that does not name an array has no LDS for it: the emission's
+// exists in the temperature instantiations only, neither in an instantiation without groups.
+__shared__ float g_group_sun[3 * kBlockThreads];
+__shared__ float g_group_em[3 * kBlockThreads];
 // A gang launch's per-wavefront state: the tile it owns, the tile's waves added to the film, the next boundary and
 // the size of the group being rendered (0: none, the wavefront claims a tile at its next fetch).
 __shared__ uint32_t g_gang[kBlockThreads / 64][4];
@@ -140,8 +150,56 @@ constexpr uint32_t kGangMaxArea = 256;
 // wavefront's scratch; every other launch compiles them out.
 // Split: the density evaluation runs as two halves of one lane_iteration (kEvalSplit, vpt_integrator.h eval_issue);
 // the kernel sets it by kernel_eval_split.
-template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false, bool Split = false>
+// Groups: light groups (vpt_gpu_set_light_groups; 1: sun and sky, 2: emission too -- a temperature grid): the
+// accumulators of env_groups (vpt_integrator.h) in LDS and three more stores per sample in film_add; every other
+// launch compiles them out.
+template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false, bool Split = false, int Groups = 0>
 struct KernelEnvT {
+  static_assert(!(Groups && (RegCold || Feed || Gang)), "light groups run the throughput kernels, plain or band");
+  static constexpr bool kGroups = Groups != 0;  // (primary_event, nee_done and the pixel block)
+  __device__ __forceinline__ void group_begin() {
+    for (int c = 0; c < 3; ++c) {
+      g_group_sun[c * kBlockThreads + threadIdx.x] = 0.0f;
+      if constexpr (Groups == 2) g_group_em[c * kBlockThreads + threadIdx.x] = 0.0f;
+    }
+  }
+  __device__ __forceinline__ void group_emit(float sc, float X, float Y, float Z) {
+    if constexpr (Groups == 2) {
+      float* const e = g_group_em + threadIdx.x;
+      e[0] = e[0] + sc * X;
+      e[kBlockThreads] = e[kBlockThreads] + sc * Y;
+      e[2 * kBlockThreads] = e[2 * kBlockThreads] + sc * Z;
+    }
+  }
+  __device__ __forceinline__ void group_sun(float pt, float l0, float l1, float l2) {
+    float* const d = g_group_sun + threadIdx.x;
+    d[0] = d[0] + pt * l0;
+    d[kBlockThreads] = d[kBlockThreads] + pt * l1;
+    d[2 * kBlockThreads] = d[2 * kBlockThreads] + pt * l2;
+  }
+  __device__ __forceinline__ void group_sun_zero() {  // D + 0.0f: a -0.0 becomes +0.0 (nee_done's select)
+    float* const d = g_group_sun + threadIdx.x;
+    for (int c = 0; c < 3; ++c) d[c * kBlockThreads] = d[c * kBlockThreads] == 0.0f ? 0.0f : d[c * kBlockThreads];
+  }
+  // The sample's group terms, at the beauty sample's offset s in the regions behind it (KernelArgs::group_stride):
+  // the same store pattern as the sample's own, three more times.  sky: the path ended in ST_FINISH (le_inf added).
+  __device__ __forceinline__ void group_store(const DevScene& S, float* s, bool sky) {
+    const uint64_t stride = args()->group_stride;
+    if constexpr (Groups == 2) {
+      float* const e = s + stride;
+      e[0] = g_group_em[threadIdx.x];
+      e[1] = g_group_em[kBlockThreads + threadIdx.x];
+      e[2] = g_group_em[2 * kBlockThreads + threadIdx.x];
+    }
+    float* const d = s + 2 * stride;
+    d[0] = g_group_sun[threadIdx.x];
+    d[1] = g_group_sun[kBlockThreads + threadIdx.x];
+    d[2] = g_group_sun[2 * kBlockThreads + threadIdx.x];
+    float* const k = s + 3 * stride;
+    k[0] = sky ? S.le_inf[0] : 0.0f;
+    k[1] = sky ? S.le_inf[1] : 0.0f;
+    k[2] = sky ? S.le_inf[2] : 0.0f;
+  }
   static_assert(!(RegCold && Split), "the latency kernels evaluate whole");
   static_assert(!(RegCold && Feed), "feeds run the throughput kernels only");
   static_assert(!(Band && Feed), "band launches are no feeds");
@@ -418,7 +476,7 @@ struct KernelEnvT {
   // A band launch stores from the lane too, at its job's address (job_start) + pixel * band_group * 3 floats: under
   // the same-tile order the wavefront's lanes are consecutive waves of one tile, whose samples of a pixel are adjacent.
   __device__ __forceinline__ bool film_regroup(const DevScene& S) const {
-    if constexpr (Band || Gang) return false;
+    if constexpr (Band || Gang || Groups != 0) return false;  // (Groups: always an ordered launch)
     if (args()->samples) return false;
     return !RegCold && (args()->samples != nullptr || (uint64_t)S.W * (uint64_t)S.H < (1ULL << 26));  // (index << 6 | lane fits 32 bits)
   }
@@ -431,6 +489,7 @@ struct KernelEnvT {
       s[0] = lc.L[0];
       s[1] = lc.L[1];
       s[2] = lc.L[2];
+      if constexpr (Groups != 0) group_store(S, s, ln.state == ST_FINISH);
       return;
     }
     if constexpr (Gang) {  // the lane's slot of the wavefront's scratch: [lane][pixel][3]
@@ -464,6 +523,7 @@ struct KernelEnvT {
       s[0] = lc.L[0];
       s[1] = lc.L[1];
       s[2] = lc.L[2];
+      if constexpr (Groups != 0) group_store(S, s, ln.state == ST_FINISH);
     } else {
       float* f = args()->film + (uint64_t)pixel * 4;
       const float r = S.imaging_ratio;
@@ -789,7 +849,7 @@ constexpr bool kernel_eval_split(bool has_temp, bool debug, bool lat) { return !
 
 // counters[] order = vpt_counters field order
 template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false,
-          bool Gang = false>
+          bool Gang = false, bool Groups = false>
 __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT : (Debug ? VPT_WAVES_SLOW : (HasTemp ? VPT_WAVES_TEMP : VPT_WAVES_FAST)))) void vpt_integrate_kernel(KernelArgs args, const DevScene* scene,
                                                                        unsigned long long* counters) {
   (void)args;  // read through KernelEnvT::args()
@@ -807,6 +867,7 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
 #endif
   static_assert(!(Band && Debug), "band launches have no records or events");
   static_assert(!(Gang && (Debug || Lat || Compact || Feed || Band)), "gang launches run the plain throughput kernels only");
+  static_assert(!(Groups && (Debug || Lat || Compact || Feed || Gang)), "light groups run the throughput kernels, plain or band");
   if constexpr (Gang) {
     if (threadIdx.x < kBlockThreads / 64) {  // no tile, no group (read by the wavefront itself: no barrier needed)
       g_gang[threadIdx.x][0] = 0xffffffffu;
@@ -814,7 +875,7 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
     }
     __syncthreads();
   }
-  KernelEnvT<Lat, Feed, Band, Gang, kernel_eval_split(HasTemp, Debug, Lat)> env;
+  KernelEnvT<Lat, Feed, Band, Gang, kernel_eval_split(HasTemp, Debug, Lat), Groups ? (HasTemp ? 2 : 1) : 0> env;
   env.reg_cold = nullptr;
   Lane ln;
   lane_init(ln);
@@ -1289,6 +1350,23 @@ __global__ __launch_bounds__(256) void vpt_dense_expand_kernel(DevGrid g, float*
       }
     }
   }
+}
+
+// vpt_gpu_relight: out.c = ((G0.c * k0.c) + (G1.c * k1.c)) + (G2.c * k2.c) for c = X, Y, Z and out.w = G0.w, per pixel,
+// fp32 in this order (the build contracts nothing); g: the three planes [3][npix] as float4, k: gains [group][XYZ].
+struct RelightGains {
+  float k[9];
+};
+__global__ __launch_bounds__(256) void vpt_relight_kernel(const float4* g, RelightGains K, uint64_t npix, float4* out) {
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npix) return;
+  const float4 a = g[p], b = g[npix + p], c = g[2 * npix + p];
+  float4 o;
+  o.x = ((a.x * K.k[0]) + (b.x * K.k[3])) + (c.x * K.k[6]);
+  o.y = ((a.y * K.k[1]) + (b.y * K.k[4])) + (c.y * K.k[7]);
+  o.z = ((a.z * K.k[2]) + (b.z * K.k[5])) + (c.z * K.k[8]);
+  o.w = a.w;
+  out[p] = o;
 }
 
 // The coverage pass (vpt_gpu_render_alpha): alpha = 1 - mean exp(-tau) over each pixel's sub-rays, tau by the

@@ -7,6 +7,9 @@
 namespace vpt {
 
 constexpr int kBlockThreads = 256;
+// Light groups (vpt_gpu_set_light_groups): regions of the sample buffer per launch -- the beauty samples, then the
+// emission, sun and sky terms, 12 bytes each per sample: 48 bytes per sample instead of 12.
+constexpr uint64_t kGroupRegions = 4;
 // Feed mode (vpt_gpu_feed_*): the published word's closed bit, an empty ring slot, a lane's "item
 // reserved, not yet published" and "waiting, nothing reserved" marks (LaneCold::pix), and how long a lane
 // waits before it gives up (s_memrealtime ticks at 100 MHz: 30 s).

@@ -55,6 +55,26 @@ def foreground_film(film: np.ndarray, alpha: np.ndarray, cfg) -> np.ndarray:
     return out
 
 
+def relight(groups: np.ndarray, gains) -> np.ndarray:
+    """The relit film of light-group planes (Integrator.set_light_groups; float32 [3][H][W][4]: emission, sun, sky)
+    under `gains` (3 x 3, [group][XYZ]; scenes.light_gains): per pixel
+
+        out.c = ((G0.c * k0.c) + (G1.c * k1.c)) + (G2.c * k2.c)   for c = X, Y, Z;     out.w = G0.w
+
+    in float32, in this order -- vpt_gpu_relight's arithmetic restated in numpy, byte for byte, so a machine without a
+    device relights a saved file (--groups-out / --relight-from)."""
+    g = np.asarray(groups, dtype=np.float32)
+    k = np.asarray(gains, dtype=np.float32).reshape(-1)
+    if g.ndim != 4 or g.shape[0] != 3 or g.shape[3] != 4 or k.size != 9:
+        raise ValueError(f"relight wants planes [3][H][W][4] and 3 x 3 gains, got {g.shape} and {k.size} gains")
+    k = k.reshape(3, 3)
+    out = np.empty(g.shape[1:], np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        out[..., :3] = ((g[0, ..., :3] * k[0]) + (g[1, ..., :3] * k[1])) + (g[2, ..., :3] * k[2])
+    out[..., 3] = g[0, ..., 3]
+    return out
+
+
 def _chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 

@@ -253,6 +253,44 @@ class Integrator:
                    "vpt_gpu_set_film_moments")
         self._m2 = m2
 
+    def set_light_groups(self, groups) -> None:
+        """Attach light-group planes (a device float32 [3][H][W][4] tensor -- emission, sun, sky, each an XYZW film;
+        None detaches): while attached, the ordered film passes also add every sample's emission, distant-light and
+        infinite-light terms into them, in wave order (vpt_gpu_set_light_groups).  Each plane is the film the
+        reference renders with the other two sources off.  The tensor is kept alive while it is attached."""
+        if groups is not None:
+            assert groups.is_cuda and groups.dtype == self.torch.float32 and groups.is_contiguous()
+            assert tuple(groups.shape) == (3, self.cfg.height, self.cfg.width, 4)
+        capi.check(capi.lib().vpt_gpu_set_light_groups(self.h, C.c_void_p(groups.data_ptr()) if groups is not None else None),
+                   "vpt_gpu_set_light_groups")
+        self._groups = groups
+
+    def relight(self, groups, gains, stream=None):
+        """The relit film [H][W][4] of group planes `groups` ([3][H][W][4]) under `gains` (3 x 3, [group][XYZ]; see
+        scenes.light_gains): out.c = ((G0.c k0.c) + (G1.c k1.c)) + (G2.c k2.c), out.w = G0.w, by one small kernel
+        (vpt_gpu_relight; image.relight is the same arithmetic in numpy).  Takes a device tensor or a numpy array and
+        returns the same kind, as denoise does; with a tensor the call is asynchronous on `stream`."""
+        torch = self.torch
+        as_numpy = not torch.is_tensor(groups)
+        H, W = self.cfg.height, self.cfg.width
+        k = np.ascontiguousarray(np.asarray(gains, dtype=np.float32).reshape(-1))
+        if k.size != 9:
+            raise ValueError("relight: gains is 3 x 3, [group][XYZ]")
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        with torch.cuda.stream(s):
+            g = groups if not as_numpy else torch.from_numpy(np.array(groups, dtype=np.float32, order="C"))
+            g = g.to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(g.shape) != (3, H, W, 4):
+                raise ValueError(f"relight: expected planes of shape {(3, H, W, 4)}, got {tuple(g.shape)}")
+            out = torch.empty((H, W, 4), dtype=torch.float32, device=self.dev)
+        capi.check(capi.lib().vpt_gpu_relight(self.h, C.c_void_p(g.data_ptr()), k.ctypes.data_as(C.POINTER(C.c_float)),
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(int(s.cuda_stream))),
+                   "vpt_gpu_relight")
+        if as_numpy:
+            s.synchronize()
+            return out.cpu().numpy()
+        return out
+
     def render_tile_list(self, tiles, first_wave: int, num_waves: int, film=None, stream=None):
         """render_tiles for an arbitrary list of tiles (strictly ascending indices < T) with one list launch
         (vpt_gpu_render_tile_list); waves are 1-based, as render_tiles."""
@@ -641,17 +679,22 @@ def run(cfg: capi.Configuration, integrator: Integrator, tp: TileProvider, film:
 
 def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, step_waves: int = 64,
                     max_waves: Optional[int] = None, abs_floor: float = 1e-3, fused: bool = False,
-                    return_moments: bool = False):
+                    return_moments: bool = False, groups: bool = False):
     """Render a frame from zero until every tile's error estimate (Integrator.tile_errors) is at most
     `target_error` or it has `max_waves` waves (None: cfg.num_waves): `min_waves` waves of every tile, then
     `step_waves` more per round of the tiles still above the target (vpt_gpu_render_adaptive).  Each tile's film
     is the uniform frame's after its own wave count, bit for bit.  fused: the one-launch driver
     (vpt_gpu_render_adaptive_fused: a wavefront owns a tile; the same bytes; tiles of at most 256 pixels).
     -> (film float32[H][W][4], waves uint32[T], err float32[T], info dict); return_moments: the film's moment plane
-    (float32[H][W], what Integrator.denoise wants beside the film) is appended."""
+    (float32[H][W], what Integrator.denoise wants beside the film) is appended.  groups: the frame's light-group planes
+    (float32[3][H][W][4], Integrator.set_light_groups) are rendered with it and appended last -- the rounds driver
+    only: the fused driver does not write them."""
     torch = it.torch
+    if groups and fused:
+        raise ValueError("render_adaptive: light groups are rendered by the rounds driver only (fused=False)")
     T = it.cfg.jobs_per_wave()
     film = torch.zeros_like(it.film)
+    gp = torch.zeros((3, it.cfg.height, it.cfg.width, 4), dtype=torch.float32, device=it.dev) if groups else None
     m2 = torch.zeros((it.cfg.height, it.cfg.width), dtype=torch.float32, device=it.dev)
     torch.cuda.synchronize(it.dev)
     p = capi.AdaptiveParams(float(target_error), float(abs_floor), int(min_waves), int(step_waves),
@@ -659,31 +702,51 @@ def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, st
     res = capi.AdaptiveResult()
     waves, err = np.zeros(T, np.uint32), np.zeros(T, np.float32)
     name = "vpt_gpu_render_adaptive_fused" if fused else "vpt_gpu_render_adaptive"
-    capi.check(getattr(capi.lib(), name)(it.h, C.byref(p), C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
-                                         waves.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                         err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res),
-                                         C.c_void_p(it.stream_handle(None))), name)
+    prev = getattr(it, "_groups", None)
+    if groups:
+        it.set_light_groups(gp)
+    try:
+        capi.check(getattr(capi.lib(), name)(it.h, C.byref(p), C.c_void_p(film.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                             waves.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             err.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res),
+                                             C.c_void_p(it.stream_handle(None))), name)
+        torch.cuda.synchronize(it.dev)
+    finally:
+        if groups:
+            it.set_light_groups(prev)
+    out = (film.cpu().numpy(), waves, err, res.as_dict())
     if return_moments:
-        return film.cpu().numpy(), waves, err, res.as_dict(), m2.cpu().numpy()
-    return film.cpu().numpy(), waves, err, res.as_dict()
+        out += (m2.cpu().numpy(),)
+    if groups:
+        out += (gp.cpu().numpy(),)
+    return out
 
 
-def render_uniform(it: Integrator, moments: bool = True):
+def render_uniform(it: Integrator, moments: bool = True, groups: bool = False):
     """The whole frame (cfg.num_waves waves of every tile) from zero as one ordered launch -- the reference's film bit
     for bit -- with a moment plane attached: -> (film [H][W][4], m2 [H][W]) device tensors (moments=False: the film
-    alone).  The context's previous plane attachment is restored afterwards."""
+    alone).  groups=True: with light-group planes attached as well (Integrator.set_light_groups), appended as a
+    [3][H][W][4] tensor: -> (film, m2, groups).  The context's previous attachments are restored afterwards."""
     torch = it.torch
     film = torch.zeros_like(it.film)
     m2 = torch.zeros((it.cfg.height, it.cfg.width), dtype=torch.float32, device=it.dev) if moments else None
+    gp = torch.zeros((3, it.cfg.height, it.cfg.width, 4), dtype=torch.float32, device=it.dev) if groups else None
     torch.cuda.synchronize(it.dev)
-    prev = getattr(it, "_m2", None)
+    prev, prev_g = getattr(it, "_m2", None), getattr(it, "_groups", None)
     it.set_film_moments(m2)
+    if groups:
+        it.set_light_groups(gp)
     try:
         it.render_waves(1, int(it.cfg.num_waves), film=film)
         torch.cuda.synchronize(it.dev)
     finally:
         it.set_film_moments(prev)
-    return (film, m2) if moments else film
+        if groups:
+            it.set_light_groups(prev_g)
+    out = (film, m2) if moments else (film,)
+    if groups:
+        out += (gp,)
+    return out if len(out) > 1 else film
 
 
 def _host_copy(x, torch):

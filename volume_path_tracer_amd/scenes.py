@@ -69,6 +69,46 @@ def orbit(cfg: capi.Configuration, frames: int, degrees: float = 360.0) -> list:
     return out
 
 
+def light_gains(cfg_rendered: capi.Configuration, cfg_wanted: capi.Configuration):
+    """The 3 x 3 relighting gains [group][XYZ] (float32; Integrator.relight, image.relight) that turn the light groups
+    rendered under cfg_rendered into cfg_wanted's picture: row 0 (emission) the le_scale ratio, row 1 (sun) the ratio
+    of distant_light.xyz * multiplier per channel, row 2 (sky) that of infinite_light.xyz * multiplier.  The products
+    are the scene's float32 ones, the ratios float64 rounded once.  A source that is zero in both gets gain 1.
+    ValueError where a rendered value is zero and the wanted one is not (nothing to scale), and when anything else
+    differs that changes the paths or the emission non-linearly: camera, medium coefficients, g, max_depth,
+    temperature scale or offset, sun direction, jitter, single-pixel mode, seed, waves, frame or tile size, volume."""
+    import numpy as np
+
+    a, b = cfg_rendered.copy(), cfg_wanted.copy()
+
+    def sources(c):
+        w, f = c.worker_parameters, np.float32
+        return np.stack([np.full(3, c.volume_parameters.le_scale, np.float32),
+                         np.asarray(w.distant_light_xyz[:], np.float32) * f(w.distant_light_multiplier),
+                         np.asarray(w.infinite_light_xyz[:], np.float32) * f(w.infinite_light_multiplier)])
+
+    have, want = sources(a), sources(b)
+    for c in (a, b):  # what is left must be the same scene
+        w = c.worker_parameters
+        c.volume_parameters.le_scale = 0.0
+        w.distant_light_multiplier = w.infinite_light_multiplier = 0.0
+        w.distant_light_xyz[:] = w.infinite_light_xyz[:] = [0.0, 0.0, 0.0]
+        c.num_workers = 0
+    if bytes(a) != bytes(b):
+        raise ValueError("light_gains: the configurations differ in more than the strength and colour of their lights "
+                         "(camera, medium, g, max_depth, temperature mapping, sun direction, seed and sizes must agree)")
+    names = ("le_scale", "distant_light", "infinite_light")
+    k = np.ones((3, 3), np.float32)
+    for g in range(3):
+        for c in range(3):
+            if have[g, c] == 0.0:
+                if want[g, c] != 0.0:
+                    raise ValueError(f"light_gains: {names[g]} channel {'XYZ'[c]} was rendered at zero: nothing to scale")
+            else:
+                k[g, c] = np.float32(np.float64(want[g, c]) / np.float64(have[g, c]))
+    return k
+
+
 _CAMERA_KEYS = {"position": 3, "look": 3, "up": 3, "vfov_deg": 1}
 
 
