@@ -423,6 +423,43 @@ int vpt_gpu_set_light_groups(vpt_gpu_ctx* ctx, float* groups_device);
 int vpt_gpu_relight(vpt_gpu_ctx* ctx, const float* groups_device, const float gains[9], float* film_out_device,
                     void* hip_stream);
 
+/* Camera motion blur: a camera per wave from a shutter table.  An entry holds the four camera fields a frame of a
+ * sequence replaces; imaging_ratio stays the scene's. */
+typedef struct vpt_shutter_camera {
+  float position[3];
+  float look[3];
+  float up[3];
+  float vfov_deg;
+} vpt_shutter_camera;
+#define VPT_SHUTTER_MAX 65536u
+
+/* Attaches a shutter of `n` cameras (1 .. VPT_SHUTTER_MAX; the library copies them), or detaches it (cams == NULL and
+ * n == 0; any other null / zero mix is VPT_E_INVALID).  A job is one tile in one wave, its wave is jid / T, and its
+ * RNG stream depends on jid alone.  While a shutter is attached, job jid of vpt_gpu_render_jobs, vpt_gpu_render_tiles
+ * and vpt_gpu_render_tile_list -- the launches they are split into under max_bytes included -- generates its primary
+ * rays (Camera::generate_ray, camera.hpp:14-23) through entry (jid / T) % n instead of the scene's camera.  Nothing
+ * else changes, no random draw included: the film is, bit for bit, the ordered fp32 sum of the films the reference
+ * renders wave by wave, wave k with the scene whose camera is entry k % n.  An attached moment plane and attached
+ * light-group planes keep their contracts on those samples.
+ * Each entry is turned into the scene's 15 camera floats by the code that derives the scene's own camera (it reads
+ * output_size besides the entry, which cannot change) and uploaded as a 64-byte row of the table.  An entry with a
+ * non-finite field, look == position, an up vector that is zero or along the view direction, or vfov_deg outside
+ * (0, 180) is VPT_E_INVALID naming its index, and the context keeps the shutter it had.
+ * A sync point like vpt_gpu_set_scene (it waits for the context's launches); VPT_E_STATE while a feed of the context
+ * or a drop-in frame is open.  The attachment survives vpt_gpu_set_scene and vpt_gpu_set_grids.
+ * Launches with a shutter run the throughput kernels' Shutter instantiations (ordered launches: it needs
+ * VPT_FILM_ORDERED).  Calls that cannot honour it fail with VPT_E_STATE while it is attached instead of rendering the
+ * still camera: vpt_gpu_render_jobs_records, vpt_gpu_trace_jobs, the pixel RNG mode, VPT_FILM_ATOMIC, a feed's
+ * launch, vpt_gpu_frame_open, vpt_gpu_render_adaptive_fused and vpt_gpu_render_alpha (its matte would be another
+ * camera's).  The tile-cost pass keeps using the scene's camera: only the schedule depends on it, never a sample. */
+int vpt_gpu_set_shutter(vpt_gpu_ctx* ctx, const vpt_shutter_camera* cams, uint32_t n);
+/* The attached shutter's entries, 0 if none. */
+int vpt_gpu_shutter_info(const vpt_gpu_ctx* ctx, uint32_t* n);
+/* One row of the shutter table as the library derives it for a width x height frame (host only, no device):
+ * out16[4 i .. 4 i + 3] = cam_L[3 i], cam_L[3 i + 1], cam_L[3 i + 2], cam_t[i] for i = 0, 1, 2 (the rows of
+ * Camera::raster_to_world_dir), out16[12 .. 14] = position, out16[15] = 0.  VPT_E_INVALID as vpt_gpu_set_shutter. */
+int vpt_shutter_entry(const vpt_shutter_camera* cam, uint32_t width, uint32_t height, float* out16);
+
 /* A tile-list launch: vpt_gpu_render_tiles for the tiles tiles[0..n) (a host array, strictly ascending, every entry
  * < T) instead of [tile_lo, tile_hi): renders the jobs (wave_begin + w) * T + tiles[i], w in [0, wave_count), adds
  * each pixel's samples in wave order and touches no pixel outside the listed tiles.  Order: the list's tiles by

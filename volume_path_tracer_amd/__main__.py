@@ -36,6 +36,18 @@ an absent group keeps 1) writes the output PNG from the relit film (Integrator.r
 saves the raw film.  ``--relight-from g.npy`` relights a saved file with the same arithmetic in numpy (image.relight)
 and opens no device: the configuration is not read.  Not with ``--denoise``, ``--alpha-foreground`` or
 ``--adaptive-fused``.
+``--shutter-camera FILE.json`` renders camera motion blur (Integrator.set_shutter): the file holds
+one camera object (a ``--camera-path`` entry), the camera at shutter close; the scene's camera is the camera at shutter
+open, and wave k renders through the camera at the k-th time of scenes.shutter_times between them.
+``--shutter-samples N`` sets the number of cameras (default ``num_waves``, at most 65536).  In a sequence with a moving
+camera (``--frames`` with an orbit, or ``--camera-path``) ``--shutter F`` (0 < F <= 1) blurs frame k from its own camera
+by the fraction F towards frame k + 1's; the last frame of a camera path extrapolates its previous step, the last
+frame of an orbit uses the rotation at index ``frames``.  The uniform frame is then one ordered launch
+(render.render_uniform), the adaptive one the rounds driver; ``--light-groups``, ``--relight`` and ``--denoise
+--denoise-no-guides`` work.  Not with ``--alpha``, ``--alpha-foreground``, ``--alpha-out``, ``--denoise`` guided by the
+matte, ``--adaptive-fused``, ``--rng-mode pixel`` or ``--event-log``: exit 1 before a device is touched.
+``--rng-mode pixel`` renders the plain uniform frame in the pixel RNG mode (one stream per pixel sample; not the
+reference's samples).
 Exits 1 on a fatal error, like vptFATAL.
 """
 from __future__ import annotations
@@ -153,6 +165,14 @@ def main(argv=None) -> int:
                     help="implies --light-groups: the output PNG from the relit film; K a number or X:Y:Z")
     ap.add_argument("--relight-from", default=None, metavar="G.npy",
                     help="relight saved planes (--groups-out) into output_path; opens no device")
+    ap.add_argument("--shutter-camera", default=None, metavar="FILE.json",
+                    help="motion blur: the camera at shutter close, one {position, look, up?, vfov_deg?} object")
+    ap.add_argument("--shutter-samples", type=int, default=None, metavar="N",
+                    help="motion blur: cameras across the shutter (default num_waves, at most 65536)")
+    ap.add_argument("--shutter", type=float, default=None, metavar="F",
+                    help="sequence: blur frame k by the fraction F (0 < F <= 1) of the move to frame k + 1's camera")
+    ap.add_argument("--rng-mode", choices=("reference", "pixel"), default="reference",
+                    help="pixel: one RNG stream per pixel sample (the plain uniform frame only)")
     args = ap.parse_args(argv)
     if (args.denoised_film_out or args.moments_out) and not args.denoise:
         ap.error("--denoised-film-out and --moments-out need --denoise")
@@ -169,6 +189,29 @@ def main(argv=None) -> int:
                 print(f"[vpt] FATAL: {flag} does not combine with --light-groups / --relight (out of scope: README, "
                       f"Light groups)", file=sys.stderr)
                 return 1
+    want_shutter = args.shutter_camera is not None or args.shutter is not None
+    if want_shutter:  # (checked before anything touches a device: these would render the still camera, or raise late)
+        for flag, on in (("--alpha", args.alpha), ("--alpha-foreground", args.alpha_foreground),
+                         ("--alpha-out", args.alpha_out), ("--denoise", args.denoise and not args.denoise_no_guides),
+                         ("--adaptive-fused", args.adaptive_fused), ("--rng-mode pixel", args.rng_mode == "pixel"),
+                         ("--event-log", args.event_log), ("--relight-from", args.relight_from)):
+            if on:
+                why = " (its matte guides are the still camera's: add --denoise-no-guides)" if flag == "--denoise" else ""
+                print(f"[vpt] FATAL: {flag} does not combine with a shutter (--shutter-camera / --shutter){why}: README, "
+                      f"Motion blur", file=sys.stderr)
+                return 1
+        if args.shutter is not None and not 0.0 < args.shutter <= 1.0:
+            print("[vpt] FATAL: --shutter wants a fraction F with 0 < F <= 1", file=sys.stderr)
+            return 1
+        if args.shutter_samples is not None and not 1 <= args.shutter_samples <= 65536:
+            print("[vpt] FATAL: --shutter-samples wants 1 .. 65536 cameras", file=sys.stderr)
+            return 1
+    elif args.shutter_samples is not None:
+        ap.error("--shutter-samples needs --shutter-camera or --shutter")
+    if args.rng_mode == "pixel" and (args.adaptive is not None or args.denoise or want_groups):
+        print("[vpt] FATAL: --rng-mode pixel renders the plain uniform frame only (not with --adaptive, --denoise or "
+              "--light-groups)", file=sys.stderr)
+        return 1
     if args.relight_from:  # host work only: no device, no configuration
         try:
             import numpy as np
@@ -193,10 +236,20 @@ def main(argv=None) -> int:
             return 1
     elif args.orbit is not None:
         ap.error("--orbit needs --frames")
+    if args.shutter is not None and (not sequence or (args.frames is None and args.camera_path is None)
+                                     or (args.volume_sequence and args.orbit is None and args.camera_path is None)):
+        print("[vpt] FATAL: --shutter blurs a sequence's frames towards the next frame's camera: it needs --frames with "
+              "an orbit, or --camera-path (a single frame takes --shutter-camera)", file=sys.stderr)
+        return 1
+    if args.shutter_camera is not None and (sequence or args.shutter is not None):
+        print("[vpt] FATAL: --shutter-camera is the single frame's camera at shutter close; a sequence takes --shutter F",
+              file=sys.stderr)
+        return 1
 
     from . import image, traces, volumes
     from .render import Integrator, TileProvider, matte_guides, render_adaptive, render_sequence, render_uniform, run
-    from .scenes import SynthGrid, orbit, read_camera_path, read_configuration, with_camera
+    from .scenes import (SynthGrid, camera_of, lerp_camera, orbit, read_camera, read_camera_path, read_configuration,
+                         shutter_cameras, with_camera)
 
     def render_frame(it, tag="", paths=None):
         """One frame's device work, as the single-frame program does it -> what write_frame saves (host arrays).
@@ -228,6 +281,13 @@ def main(argv=None) -> int:
                   f"{info['tiles_at_max']} tiles at the cap, max tile error {info['max_error']:.4g}", file=sys.stderr)
             res["waves"] = waves
             emit("waves")
+        elif args.rng_mode == "pixel":  # (feeds run the reference RNG mode: plain launches, film atomics)
+            dev_film = it.torch.zeros_like(it.film)
+            it.render_waves(1, int(cfg.num_waves), film=dev_film)
+            film = dev_film.cpu().numpy()
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp, pixel RNG mode)",
+                  file=sys.stderr)
         elif args.denoise:  # the ordered frame with its moment plane (the feed keeps none)
             film, m2 = (t.cpu().numpy() for t in render_uniform(it))
             ms = (time.perf_counter() - t0) * 1e3
@@ -238,6 +298,11 @@ def main(argv=None) -> int:
             ms = (time.perf_counter() - t0) * 1e3
             print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp, light groups)",
                   file=sys.stderr)
+        elif want_shutter:  # the ordered frame: a feed's launch does not honour the shutter
+            film = render_uniform(it, moments=False).cpu().numpy()
+            ms = (time.perf_counter() - t0) * 1e3
+            print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp, a shutter "
+                  f"of {it.shutter_info()} cameras)", file=sys.stderr)
         else:
             tp = TileProvider(cfg.output_size, cfg.num_waves, cfg.tile_size)
             tp.reset_eta()
@@ -340,8 +405,14 @@ def main(argv=None) -> int:
         if temp is not None and temp.leaf_count:
             print(f"TempMin: {float(temp.leaf_values.min())}, TempMax: {float(temp.leaf_values.max())}")
 
+        n_shutter = min(int(cfg.num_waves), 65536) if args.shutter_samples is None else args.shutter_samples
         if not sequence:
+            close = read_camera(args.shutter_camera) if args.shutter_camera is not None else None
             it = Integrator(cfg, dens, temp, device=args.device)
+            if args.rng_mode == "pixel":
+                it.set_rng_mode(1)
+            if close is not None:
+                it.set_shutter(shutter_cameras(camera_of(cfg), camera_of(with_camera(cfg, **close)), n_shutter))
             render_frame(it, paths=outputs)
             return 0
 
@@ -351,12 +422,23 @@ def main(argv=None) -> int:
             if args.frames is not None and args.frames != len(cams):
                 raise ValueError(f"--frames {args.frames} but {args.camera_path} holds {len(cams)} cameras")
             cfgs = [with_camera(cfg, **c) for c in cams]
+            # (--shutter: the last frame closes where its previous step, repeated, would lead; one frame: nowhere)
+            last, prev = camera_of(cfgs[-1]), camera_of(cfgs[-2] if len(cfgs) > 1 else cfgs[-1])
+            closing = lerp_camera(prev, last, 2.0)
         elif args.orbit is not None or not args.volume_sequence:
-            cfgs = orbit(cfg, args.frames, 360.0 if args.orbit is None else args.orbit)
+            cfgs = orbit(cfg, args.frames, 360.0 if args.orbit is None else args.orbit, closing=args.shutter is not None)
+            closing = camera_of(cfgs.pop()) if args.shutter is not None else None
         else:
             cfgs = [None] * args.frames  # (the volume alone changes)
         nframes = len(cfgs)
+        shutters = None
+        if args.shutter is not None:  # frame k: from its own camera by the fraction F towards frame k + 1's
+            opens = [camera_of(c) for c in cfgs]
+            shutters = [shutter_cameras(a, lerp_camera(a, b, args.shutter), n_shutter)
+                        for a, b in zip(opens, opens[1:] + [closing])]
         it = Integrator(cfgs[0] if cfgs[0] is not None else cfg, dens, temp, device=args.device)
+        if args.rng_mode == "pixel":
+            it.set_rng_mode(1)
         t_seq = time.perf_counter()
 
         def frames():
@@ -367,7 +449,14 @@ def main(argv=None) -> int:
                 yield cfgs[k], vol
 
         count = iter(range(nframes))
-        stats = render_sequence(it, frames(), lambda i: render_frame(i, f"frame {next(count)}: "),
+
+        def sequence_frame(i):
+            k = next(count)
+            if shutters is not None:
+                i.set_shutter(shutters[k])
+            return render_frame(i, f"frame {k}: ")
+
+        stats = render_sequence(it, frames(), sequence_frame,
                                 lambda k, res: write_frame(res, {n: (_frame_path(p, k) if p else p)
                                                                  for n, p in outputs.items()}))
         total = (time.perf_counter() - t_seq) * 1e3

@@ -25,6 +25,14 @@ class CameraParams(C.Structure):
                 ("vfov_deg", C.c_float), ("imaging_ratio", C.c_float)]
 
 
+class ShutterCamera(C.Structure):
+    """vpt_shutter_camera: one entry of a shutter (vpt_gpu_set_shutter) -- the camera fields a frame replaces."""
+    _fields_ = [("position", C.c_float * 3), ("look", C.c_float * 3), ("up", C.c_float * 3), ("vfov_deg", C.c_float)]
+
+
+VPT_SHUTTER_MAX = 65536
+
+
 class WorkerParams(C.Structure):
     _fields_ = [("single_pixel_enabled", C.c_int32), ("use_jitter", C.c_int32),
                 ("single_pixel_coord", C.c_int64 * 2),
@@ -294,6 +302,10 @@ def lib() -> C.CDLL:
     if hasattr(L, "vpt_gpu_set_light_groups"):  # (older builds in A/B runs lack the light groups)
         L.vpt_gpu_set_light_groups.argtypes = [vp, vp]
         L.vpt_gpu_relight.argtypes = [vp, vp, fp, vp, vp]
+    if hasattr(L, "vpt_gpu_set_shutter"):  # (older builds in A/B runs lack the shutter)
+        L.vpt_gpu_set_shutter.argtypes = [vp, C.POINTER(ShutterCamera), C.c_uint32]
+        L.vpt_gpu_shutter_info.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.vpt_shutter_entry.argtypes = [C.POINTER(ShutterCamera), C.c_uint32, C.c_uint32, fp]
     if hasattr(L, "vpt_gpu_render_alpha"):  # (older builds in A/B runs lack the coverage pass)
         L.vpt_gpu_render_alpha.argtypes = [vp, C.c_uint32, vp, vp, vp]
     if hasattr(L, "vpt_gpu_denoise"):  # (older builds in A/B runs lack the denoiser)

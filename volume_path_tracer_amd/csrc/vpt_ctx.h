@@ -171,6 +171,10 @@ struct vpt_gpu_ctx {
   // The light-group planes (vpt_gpu_set_light_groups): the caller's float[3][H][W][4] (emission, sun, sky), written
   // by the ordered film passes while attached.
   float* groups = nullptr;
+  // The shutter (vpt_gpu_set_shutter): the caller's cameras as copied, and their table on the device, 16 floats per
+  // entry (vpt::shutter_entry), read per lane by the kernels' Shutter instantiations.  Empty / nullptr: none attached.
+  std::vector<vpt_shutter_camera> shutter;
+  float* shutter_dev = nullptr;
   // Gang launches (vpt_gpu_render_adaptive_fused): the wavefronts' sample scratch (wavefronts x tile_area x 64 x 3
   // floats, grown when the grid does) and the tiles' wave counts (T words; their errors go to tile_err).  Allocated
   // by the first call, freed with the context.

@@ -128,6 +128,9 @@ int feed_open(vpt_gpu_ctx* ctx, float* film_device, void* hip_stream, uint64_t w
   if (!ctx || !out || (!hip_stream && !stage)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_feed_open: null argument");
   *out = nullptr;
   if (ctx->scene.pixel_mode) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_feed_open: feeds run the reference RNG mode");
+  if (!ctx->shutter.empty())  // (a feed's launch cannot honour it: refused here, before anything is set up)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_feed_open: a shutter is attached and feeds render the scene's camera: "
+                                       "detach it (vpt_gpu_set_shutter NULL, 0)");
   int rc = ctx_device(ctx);
   if (rc) return rc;
   const uint64_t cap = feed_cap(ctx, window);

@@ -285,6 +285,7 @@ void destroy(vpt_gpu_ctx* ctx) {
   (void)hipFree(ctx->perm);
   (void)hipFree(ctx->samples);
   (void)hipFree(ctx->frame_film);
+  (void)hipFree(ctx->shutter_dev);
   if (ctx->samples_done) (void)hipEventDestroy(ctx->samples_done);
   if (ctx->denoise_done) (void)hipEventDestroy(ctx->denoise_done);
   for (uint32_t i = 0; i < kLaunchSlots; ++i)
@@ -487,6 +488,17 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
                                                        : records || events ? "a debug launch"
                                                                            : "not an ordered launch of the reference RNG mode") +
                                            "): detach them (vpt_gpu_set_light_groups NULL)");
+  // The shutter (vpt_gpu_set_shutter): honoured by the ordered production launches' Shutter kernels only; any other
+  // launch fails instead of rendering the still camera.
+  const bool shutter = !ctx->shutter.empty();
+  if (shutter && (feed || !ordered || ctx->frame_waves))
+    return vpt::set_error(VPT_E_STATE, "render: a shutter is attached and this launch cannot honour it (" +
+                                           std::string(feed ? "a feed's launch"
+                                                       : ctx->frame_waves ? "a frame is open"
+                                                       : records || events ? "a debug launch"
+                                                       : ctx->scene.pixel_mode ? "the pixel RNG mode"
+                                                                               : "VPT_FILM_ATOMIC") +
+                                           "): detach it (vpt_gpu_set_shutter NULL, 0)");
   if (ordered && !band) {  // (vpt_gpu_render_tiles splits its launches itself: by waves)
     const uint64_t max_jobs = std::min<uint64_t>(ordered_cap(ctx, jid_count * per_job) / per_job, 0xffffffffULL);
     if (max_jobs == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one job's samples");
@@ -572,8 +584,8 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // wave instructions to launches that are issue-bound; r04k, profiles/archive/r04k_lat_gated_ab.txt).  lat_mode 1
   // forces it.  Same jobs, same samples.
   const uint64_t lat_blocks = cus * (uint64_t)ctx->lat_per_cu;
-  // (a launch with light groups always takes the throughput kernel: samples do not depend on the kernel)
-  const bool use_lat = !dbg && !feed && !groups && ctx->lat_mode != 0 &&
+  // (a launch with light groups or a shutter always takes the throughput kernel: samples do not depend on the kernel)
+  const bool use_lat = !dbg && !feed && !groups && !shutter && ctx->lat_mode != 0 &&
                        (ctx->lat_mode == 1 || (!ctx->grid_user && (latency || blocks <= lat_blocks)));
   if (use_lat) blocks = (uint32_t)std::min<uint64_t>(latency ? lat_blocks : blocks, lat_blocks);
   // Live-path compaction (vpt_gpu_set_compaction): partly filled launches of the latency kernel whose grid fits
@@ -628,6 +640,11 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   if (groups && !samples)
     return vpt::set_error(VPT_E_STATE, "render: light groups are attached and the sample buffer would have to grow while "
                                        "a feed of the context is open (the launch would add with film atomics)");
+  if (shutter && !samples)
+    return vpt::set_error(VPT_E_STATE, "render: a shutter is attached and the sample buffer would have to grow while a "
+                                       "feed of the context is open (the launch would add with film atomics)");
+  env.shutter = ctx->shutter_dev;
+  env.shutter_n = (uint32_t)ctx->shutter.size();
   env.samples = samples;
   env.group_stride = band ? vpt::band_sample_floats(band->tiles, band->waves, ctx->scene.tile_area, band->group)
                           : jid_count * (uint64_t)ctx->scene.tile_area * 3;
@@ -700,7 +717,26 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   // first slots would leave the fetching slots to finished ones)
   const vpt::DevScene* scene =
       latency || (use_lat && ctx->lat_ungated && !compact) ? ctx->scene_lat_dev : ctx->scene_dev;
-  if (groups) {  // the Groups instantiations of the throughput kernels, plain or band (never a debug launch)
+  if (shutter) {  // the Shutter instantiations of the throughput kernels, plain or band, with or without Groups
+    using vpt::vpt_integrate_kernel;
+    auto pick = [&](auto plain, auto runs, auto with_temp) { return temp ? with_temp : ctx->use_runs ? runs : plain; };
+    auto kernel = groups ? (band ? pick(vpt_integrate_kernel<false, false, false, false, false, false, true, false, true, true>,
+                                        vpt_integrate_kernel<false, false, true, false, false, false, true, false, true, true>,
+                                        vpt_integrate_kernel<true, false, false, false, false, false, true, false, true, true>)
+                                 : pick(vpt_integrate_kernel<false, false, false, false, false, false, false, false, true, true>,
+                                        vpt_integrate_kernel<false, false, true, false, false, false, false, false, true, true>,
+                                        vpt_integrate_kernel<true, false, false, false, false, false, false, false, true, true>))
+                         : (band ? pick(vpt_integrate_kernel<false, false, false, false, false, false, true, false, false, true>,
+                                        vpt_integrate_kernel<false, false, true, false, false, false, true, false, false, true>,
+                                        vpt_integrate_kernel<true, false, false, false, false, false, true, false, false, true>)
+                                 : pick(vpt_integrate_kernel<false, false, false, false, false, false, false, false, false, true>,
+                                        vpt_integrate_kernel<false, false, true, false, false, false, false, false, false, true>,
+                                        vpt_integrate_kernel<true, false, false, false, false, false, false, false, false, true>));
+    if (scene == ctx->scene_dev) scene = ctx->scene_full_dev;  // (the full-launch gates, as below)
+    // (light groups without a temperature grid: region 1 is the host's, as below)
+    if (groups && !temp) VPT_HIP(hipMemsetAsync(samples + env.group_stride, 0, env.group_stride * sizeof(float), s));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
+  } else if (groups) {  // the Groups instantiations of the throughput kernels, plain or band (never a debug launch)
     auto kernel = band ? (temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, true, false, true>
                           : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, true, false, true>
                                           : vpt::vpt_integrate_kernel<false, false, false, false, false, false, true, false, true>)
@@ -1313,6 +1349,9 @@ int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, fl
   if (rc) return rc;
   if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
     return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_alpha: a feed of this context is open");
+  if (!ctx->shutter.empty())
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_alpha: a shutter is attached and the matte would be the scene "
+                                       "camera's alone: detach it (vpt_gpu_set_shutter NULL, 0)");
   if (!ctx->volume_ok) return volume_gone();
   if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
   const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
@@ -1472,6 +1511,47 @@ int vpt_gpu_relight(vpt_gpu_ctx* ctx, const float* groups_device, const float ga
   return VPT_OK;
 }
 
+int vpt_gpu_set_shutter(vpt_gpu_ctx* ctx, const vpt_shutter_camera* cams, uint32_t n) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_shutter: null context");
+  if ((cams == nullptr) != (n == 0))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_shutter: cameras and a count of 1 .. 65536, or NULL and 0 to detach");
+  if (n > VPT_SHUTTER_MAX) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_shutter: more than 65536 entries");
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_shutter: a feed of this context is open");
+  if (ctx->frame_waves) return vpt::set_error(VPT_E_STATE, "vpt_gpu_set_shutter: a frame is open");
+  // The table is built aside: an entry that fails leaves the context's shutter as it was.
+  std::vector<float> table((size_t)n * 16);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (const char* why = vpt::camera_invalid(cams[i].position, cams[i].look, cams[i].up, cams[i].vfov_deg))
+      return vpt::set_error(VPT_E_INVALID, "vpt_gpu_set_shutter: entry " + std::to_string(i) + ": " + why);
+    vpt::shutter_entry(cams[i], ctx->scene.W, ctx->scene.H, table.data() + (size_t)i * 16);
+  }
+  float* dev = nullptr;
+  if (n) {
+    VPT_HIP(hipMalloc(&dev, table.size() * sizeof(float)));  // (256-byte aligned: every entry on a 64-byte line)
+    const hipError_t e = hipMemcpy(dev, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(dev);
+      return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_set_shutter: upload: ") + hipGetErrorString(e));
+    }
+  }
+  if ((rc = wait_ctx(ctx))) {  // (launches in flight read the table about to be freed)
+    if (dev) (void)hipFree(dev);
+    return rc;
+  }
+  if (ctx->shutter_dev) (void)hipFree(ctx->shutter_dev);
+  ctx->shutter_dev = dev;
+  ctx->shutter.assign(cams, cams + n);
+  return VPT_OK;
+}
+
+int vpt_gpu_shutter_info(const vpt_gpu_ctx* ctx, uint32_t* n) {
+  if (!ctx || !n) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_shutter_info: null argument");
+  *n = (uint32_t)ctx->shutter.size();
+  return VPT_OK;
+}
+
 int vpt_gpu_tile_errors(vpt_gpu_ctx* ctx, const float* film_device, const float* m2_device, float abs_floor,
                         float* err_T_host, void* hip_stream) {
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_tile_errors: null context");
@@ -1563,6 +1643,9 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
                                          ">= min_waves, target_error >= 0 and abs_floor > 0");
   int rc = ctx_device(ctx);
   if (rc) return rc;
+  if (!ctx->shutter.empty())
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: a shutter is attached and gang launches do not honour "
+                                       "it: detach it (vpt_gpu_set_shutter NULL, 0) or use vpt_gpu_render_adaptive");
   if (ctx->groups)
     return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_adaptive_fused: light groups are attached and gang launches do not "
                                        "write them: detach them (vpt_gpu_set_light_groups NULL) or use vpt_gpu_render_adaptive");
@@ -1988,6 +2071,9 @@ int vpt_gpu_frame_open(vpt_gpu_ctx* ctx, uint64_t jid_lo, uint64_t* waves_io, ui
   if (S.pixel_mode) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_frame_open: frames run the reference RNG mode");
   ctx->frame_waves = 0;
   if (waves == 0) return VPT_OK;
+  if (!ctx->shutter.empty())
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_frame_open: a shutter is attached and a frame's feeds render the scene's "
+                                       "camera: detach it (vpt_gpu_set_shutter NULL, 0)");
   if (tile_lo >= tile_hi || tile_hi > S.T) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_frame_open: bad tile range");
   const uint64_t per_wave = (uint64_t)(tile_hi - tile_lo) * (uint64_t)S.tile_area * 3 * sizeof(float);
   // as many of the waves asked for as fit 3/4 of the device's free memory (the buffer already held counted in), at

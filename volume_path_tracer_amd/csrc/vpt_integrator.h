@@ -1031,6 +1031,20 @@ struct env_groups<Env, decltype((void)Env::kGroups)> {
   static constexpr bool value = Env::kGroups;
 };
 
+// Env::kShutter, false for an environment without one: a camera per wave (vpt_gpu_set_shutter).  When a lane takes
+// job jid it tells the environment the job's entry of the shutter table, (jid / T) % shutter_n (shutter_begin), and
+// the pixel block reads the three rows of Camera::raster_to_world_dir and the position from that entry
+// (shutter_row(r): cam_L[3 r], cam_L[3 r + 1], cam_L[3 r + 2], cam_t[r]; row 3: cam_pos) instead of from the scene.
+// The expressions and their order are the scene camera's; no draw moves.
+template <class Env, class = void>
+struct env_shutter {
+  static constexpr bool value = false;
+};
+template <class Env>
+struct env_shutter<Env, decltype((void)Env::kShutter)> {
+  static constexpr bool value = Env::kShutter;
+};
+
 // A primary ray's real-or-null collision (worker.cpp:148-188) at the index point pi with density
 // dens: emission (HasTemp), then sample_discrete({Null, Absorption, Scatter}, u) with
 // p_a = sigma_a*dens/sigma_maj, p_s = sigma_s*dens/sigma_maj.  u < 0: draw the event's uniform here
@@ -1565,6 +1579,7 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
         env.job_start(S, lc, jid);  // (a feed launch with an ordered frame: the job's slot there)
       }
       uint64_t tile = jid % S.T;
+      if constexpr (env_shutter<Env>::value) env.shutter_begin((uint32_t)((jid / S.T) % env.args()->shutter_n));
       lc.x0 = (int32_t)(tile % S.ntx) * S.tw;  // TileProvider::compute_tile_rect
       lc.y0 = (int32_t)(tile / S.ntx) * S.th;
       lc.pix = S.pixel_mode ? (int32_t)p | kOnePixel : 0;
@@ -1621,6 +1636,12 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
       // Camera::generate_ray (camera.hpp:14-23)
       float rx = ((float)px + 0.5f) + jx, ry = ((float)py + 0.5f) + jy;
       float dv[3];
+      if constexpr (env_shutter<Env>::value) {  // (the wave's camera: row i holds cam_L[i * 3 ..] and cam_t[i])
+        for (int i = 0; i < 3; ++i) {
+          const float4 row = env.shutter_row(i);
+          dv[i] = row.w + (row.x * rx + (row.y * ry + row.z * 0.0f));
+        }
+      } else
       for (int i = 0; i < 3; ++i) dv[i] = S.cam_t[i] + (S.cam_L[i * 3] * rx + (S.cam_L[i * 3 + 1] * ry + S.cam_L[i * 3 + 2] * 0.0f));
       float n2 = dv[0] * dv[0] + (dv[1] * dv[1] + dv[2] * dv[2]);
       if (n2 > 0.0f) {
@@ -1629,6 +1650,16 @@ __host__ __device__ __forceinline__ void lane_iteration(ScenePtr sp, Lane& ln, E
         dv[1] = math::div_by_recip(dv[1], s, rs);
         dv[2] = math::div_by_recip(dv[2], s, rs);
       }
+      if constexpr (env_shutter<Env>::value) {
+        const float4 pos = env.shutter_row(3);
+        lc.ro[0] = pos.x;
+        lc.ro[1] = pos.y;
+        lc.ro[2] = pos.z;
+        for (int i = 0; i < 3; ++i) {
+          lc.rd[i] = dv[i];
+          lc.L[i] = 0.0f;
+        }
+      } else
       for (int i = 0; i < 3; ++i) {
         lc.ro[i] = S.cam_pos[i];
         lc.rd[i] = dv[i];

@@ -94,6 +94,17 @@ float host_value_at(const HostGrid& g, int32_t i, int32_t j, int32_t k);
 // Fills the scene constants (camera matrix, light terms, ...) for a configuration.
 int build_scene(const vpt_configuration& cfg, DevScene& S);
 
+// The camera part of build_scene (Camera::Camera): DevScene's cam_L, cam_t and cam_pos of a camera on a W x H raster.
+// build_scene calls it for the scene's camera, shutter_entry for every entry of a shutter table.
+void camera_derive(const float position[3], const float look[3], const float up[3], float vfov_deg, int64_t W, int64_t H,
+                   float cam_L[9], float cam_t[3], float cam_pos[3]);
+// nullptr for a camera camera_derive makes a camera of, else what is wrong with it (vpt_gpu_set_shutter's validation).
+const char* camera_invalid(const float position[3], const float look[3], const float up[3], float vfov_deg);
+// One entry of the device's shutter table (vpt_gpu_set_shutter; kShutterEntryFloats floats, 64-byte aligned): a row
+// per direction component, so that the pixel block's dv[i] needs one 16-byte load --
+//   [4 i .. 4 i + 3] = cam_L[3 i], cam_L[3 i + 1], cam_L[3 i + 2], cam_t[i]   (i = 0, 1, 2),   [12 .. 14] = cam_pos, [15] = 0.
+void shutter_entry(const vpt_shutter_camera& cam, int64_t W, int64_t H, float out[16]);
+
 // Blackbody table from the embedded CIE 1931 data (init_blackbody_radiation_xyz).
 void blackbody_table(float* out_500x3);
 const float* cie_table();  // [471][3]

@@ -117,6 +117,10 @@ struct KernelArgs {
   // sample's emission, sun and sky terms at the same offset in regions 1, 2, 3 (a launch without a temperature grid
   // leaves region 1 to the host, which zeroes it).  The film passes then run once per region.
   uint64_t group_stride;
+  // The shutter (vpt_gpu_set_shutter; the kernels' Shutter instantiations only): shutter_n entries of 16 floats
+  // (vpt::shutter_entry: 64-byte rows), the camera of wave w being entry w % shutter_n.
+  const float* shutter;
+  uint32_t shutter_n;
 };
 typedef const __attribute__((address_space(4))) KernelArgs* ArgsPtr;
 // This workgroup's event counters and (VPT_PROFILE builds) section cycles; the temperature kernel's LDS copy of
@@ -133,6 +137,9 @@ __shared__ uint32_t g_film_rank[kBlockThreads];
 // exists in the temperature instantiations only, neither in an instantiation without groups.
 __shared__ float g_group_sun[3 * kBlockThreads];
 __shared__ float g_group_em[3 * kBlockThreads];
+// The shutter (KernelEnvT<.., Shutter>): the float offset of the lane's entry in the shutter table, one more dword of
+// cold state beside LaneCold for the same reason: an LDS array only the Shutter instantiations name.
+__shared__ uint32_t g_shutter_at[kBlockThreads];
 // A gang launch's per-wavefront state: the tile it owns, the tile's waves added to the film, the next boundary and
 // the size of the group being rendered (0: none, the wavefront claims a tile at its next fetch).
 __shared__ uint32_t g_gang[kBlockThreads / 64][4];
@@ -153,8 +160,20 @@ constexpr uint32_t kGangMaxArea = 256;
 // Groups: light groups (vpt_gpu_set_light_groups; 1: sun and sky, 2: emission too -- a temperature grid): the
 // accumulators of env_groups (vpt_integrator.h) in LDS and three more stores per sample in film_add; every other
 // launch compiles them out.
-template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false, bool Split = false, int Groups = 0>
+// Shutter: a camera per wave (vpt_gpu_set_shutter): the lane keeps its job's table offset (shutter_begin, the fetch
+// block) and the pixel block reads the camera from the lane's entry (shutter_row) instead of the scene; every other
+// launch compiles both out.
+template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false, bool Split = false, int Groups = 0,
+          bool Shutter = false>
 struct KernelEnvT {
+  static_assert(!(Shutter && (RegCold || Feed || Gang)), "a shutter runs the throughput kernels, plain or band");
+  static constexpr bool kShutter = Shutter;  // (lane_iteration's fetch and pixel blocks)
+  __device__ __forceinline__ void shutter_begin(uint32_t entry) { g_shutter_at[threadIdx.x] = entry * 16u; }
+  // Row r of the lane's entry (16 bytes, one load per lane: a wavefront's lanes hold up to 64 different entries).
+  // Loaded where it is used, per pixel: the table stays in the caches, the registers stay the walk's.
+  __device__ __forceinline__ float4 shutter_row(int r) const {
+    return reinterpret_cast<const float4*>(args()->shutter + g_shutter_at[threadIdx.x])[r];
+  }
   static_assert(!(Groups && (RegCold || Feed || Gang)), "light groups run the throughput kernels, plain or band");
   static constexpr bool kGroups = Groups != 0;  // (primary_event, nee_done and the pixel block)
   __device__ __forceinline__ void group_begin() {
@@ -476,7 +495,7 @@ struct KernelEnvT {
   // A band launch stores from the lane too, at its job's address (job_start) + pixel * band_group * 3 floats: under
   // the same-tile order the wavefront's lanes are consecutive waves of one tile, whose samples of a pixel are adjacent.
   __device__ __forceinline__ bool film_regroup(const DevScene& S) const {
-    if constexpr (Band || Gang || Groups != 0) return false;  // (Groups: always an ordered launch)
+    if constexpr (Band || Gang || Groups != 0 || Shutter) return false;  // (Groups, Shutter: always an ordered launch)
     if (args()->samples) return false;
     return !RegCold && (args()->samples != nullptr || (uint64_t)S.W * (uint64_t)S.H < (1ULL << 26));  // (index << 6 | lane fits 32 bits)
   }
@@ -849,7 +868,7 @@ constexpr bool kernel_eval_split(bool has_temp, bool debug, bool lat) { return !
 
 // counters[] order = vpt_counters field order
 template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false,
-          bool Gang = false, bool Groups = false>
+          bool Gang = false, bool Groups = false, bool Shutter = false>
 __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT : (Debug ? VPT_WAVES_SLOW : (HasTemp ? VPT_WAVES_TEMP : VPT_WAVES_FAST)))) void vpt_integrate_kernel(KernelArgs args, const DevScene* scene,
                                                                        unsigned long long* counters) {
   (void)args;  // read through KernelEnvT::args()
@@ -868,6 +887,7 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
   static_assert(!(Band && Debug), "band launches have no records or events");
   static_assert(!(Gang && (Debug || Lat || Compact || Feed || Band)), "gang launches run the plain throughput kernels only");
   static_assert(!(Groups && (Debug || Lat || Compact || Feed || Gang)), "light groups run the throughput kernels, plain or band");
+  static_assert(!(Shutter && (Debug || Lat || Compact || Feed || Gang)), "a shutter runs the throughput kernels, plain or band");
   if constexpr (Gang) {
     if (threadIdx.x < kBlockThreads / 64) {  // no tile, no group (read by the wavefront itself: no barrier needed)
       g_gang[threadIdx.x][0] = 0xffffffffu;
@@ -875,7 +895,7 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
     }
     __syncthreads();
   }
-  KernelEnvT<Lat, Feed, Band, Gang, kernel_eval_split(HasTemp, Debug, Lat), Groups ? (HasTemp ? 2 : 1) : 0> env;
+  KernelEnvT<Lat, Feed, Band, Gang, kernel_eval_split(HasTemp, Debug, Lat), Groups ? (HasTemp ? 2 : 1) : 0, Shutter> env;
   env.reg_cold = nullptr;
   Lane ln;
   lane_init(ln);

@@ -114,6 +114,63 @@ int default_threads() {
   return n;
 }
 
+// Camera::Camera (src/camera.cpp:45-57): the raster-to-world direction map (linear part L row-major, translation t)
+// and the position of a camera on a W x H raster.  The one derivation: build_scene's for the scene's camera and
+// vpt_gpu_set_shutter's for every entry of a shutter table.
+void camera_derive(const float position[3], const float look_at[3], const float up_dir[3], float vfov_deg, int64_t W,
+                   int64_t H, float cam_L[9], float cam_t[3], float cam_pos[3]) {
+  // camera_to_world (camera.cpp:5-19)
+  F3 pos{position[0], position[1], position[2]};
+  F3 look{look_at[0], look_at[1], look_at[2]};
+  F3 up{up_dir[0], up_dir[1], up_dir[2]};
+  F3 dir = normalized(F3{look.x - pos.x, look.y - pos.y, look.z - pos.z});
+  F3 left = cross(normalized(up), dir);
+  F3 new_up = cross(dir, left);
+  float Cm[9] = {left.x, new_up.x, dir.x, left.y, new_up.y, dir.y, left.z, new_up.z, dir.z};
+  // screen_to_camera (camera.cpp:34-43), raster_to_screen (camera.cpp:21-32)
+  float ar = static_cast<float>(W) / static_cast<float>(H);
+  float vfov_rad = 3.14159274f * vfov_deg / 180.0f;
+  float tv = std::tan(vfov_rad / 2);
+  float Sl[9] = {ar * tv, 0, 0, 0, tv, 0, 0, 0, 0}, St[3] = {0.0f, 0.0f, 1.0f};
+  float hx = static_cast<float>(W) / 2.0f, hy = static_cast<float>(H) / 2.0f;
+  float Rl[9] = {-(1.0f / hx), 0, 0, 0, -(1.0f / hy), 0, 0, 0, 0}, Rt[3] = {1.0f, 1.0f, 0.0f};
+  // m_screen_to_world_dir = c2w.linear() * s2c ; m_raster_to_world_dir = m_screen_to_world_dir * r2s
+  float SWl[9], SWt[3], tmp[3];
+  mat3_mul(Cm, Sl, SWl);
+  mat3_vec(Cm, St, SWt);
+  mat3_mul(SWl, Rl, cam_L);
+  mat3_vec(SWl, Rt, tmp);
+  for (int i = 0; i < 3; ++i) cam_t[i] = tmp[i] + SWt[i];
+  cam_pos[0] = pos.x;
+  cam_pos[1] = pos.y;
+  cam_pos[2] = pos.z;
+}
+
+// What a camera must satisfy for camera_derive's result to be a camera: finite fields, a view direction (look !=
+// position), an up vector that is neither zero nor along it, 0 < vfov_deg < 180.  (build_scene does not apply it: a
+// scene file's camera is taken as it is, as the reference takes it.)  nullptr: valid; else what is wrong.
+const char* camera_invalid(const float position[3], const float look_at[3], const float up_dir[3], float vfov_deg) {
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(position[i]) || !std::isfinite(look_at[i]) || !std::isfinite(up_dir[i])) return "a field is not finite";
+  if (!(vfov_deg > 0.0f && vfov_deg < 180.0f)) return "vfov_deg is not in (0, 180)";
+  if (position[0] == look_at[0] && position[1] == look_at[1] && position[2] == look_at[2]) return "look equals position";
+  F3 dir = normalized(F3{look_at[0] - position[0], look_at[1] - position[1], look_at[2] - position[2]});
+  F3 left = cross(normalized(F3{up_dir[0], up_dir[1], up_dir[2]}), dir);
+  if (left.x == 0.0f && left.y == 0.0f && left.z == 0.0f) return "up is zero or parallel to the view direction";
+  return nullptr;
+}
+
+void shutter_entry(const vpt_shutter_camera& cam, int64_t W, int64_t H, float out[16]) {
+  float L[9], t[3], pos[3];
+  camera_derive(cam.position, cam.look, cam.up, cam.vfov_deg, W, H, L, t, pos);
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) out[4 * i + j] = L[3 * i + j];
+    out[4 * i + 3] = t[i];
+    out[12 + i] = pos[i];
+  }
+  out[15] = 0.0f;
+}
+
 // Camera::Camera (src/camera.cpp:45-57) and the constant terms of vpt::run / sample_Ld.
 int build_scene(const vpt_configuration& cfg, DevScene& S) {
   std::memset(&S, 0, sizeof S);
@@ -138,32 +195,8 @@ int build_scene(const vpt_configuration& cfg, DevScene& S) {
   S.sp_y = (int32_t)P.single_pixel_coord[1];
   S.jitter_scale = P.use_jitter ? 0.5f : 0.0f;
 
-  // camera_to_world (camera.cpp:5-19)
   const vpt_camera_params& cp = cfg.camera_parameters;
-  F3 pos{cp.position[0], cp.position[1], cp.position[2]};
-  F3 look{cp.look[0], cp.look[1], cp.look[2]};
-  F3 up{cp.up[0], cp.up[1], cp.up[2]};
-  F3 dir = normalized(F3{look.x - pos.x, look.y - pos.y, look.z - pos.z});
-  F3 left = cross(normalized(up), dir);
-  F3 new_up = cross(dir, left);
-  float Cm[9] = {left.x, new_up.x, dir.x, left.y, new_up.y, dir.y, left.z, new_up.z, dir.z};
-  // screen_to_camera (camera.cpp:34-43), raster_to_screen (camera.cpp:21-32)
-  float ar = static_cast<float>(W) / static_cast<float>(H);
-  float vfov_rad = 3.14159274f * cp.vfov_deg / 180.0f;
-  float tv = std::tan(vfov_rad / 2);
-  float Sl[9] = {ar * tv, 0, 0, 0, tv, 0, 0, 0, 0}, St[3] = {0.0f, 0.0f, 1.0f};
-  float hx = static_cast<float>(W) / 2.0f, hy = static_cast<float>(H) / 2.0f;
-  float Rl[9] = {-(1.0f / hx), 0, 0, 0, -(1.0f / hy), 0, 0, 0, 0}, Rt[3] = {1.0f, 1.0f, 0.0f};
-  // m_screen_to_world_dir = c2w.linear() * s2c ; m_raster_to_world_dir = m_screen_to_world_dir * r2s
-  float SWl[9], SWt[3], tmp[3];
-  mat3_mul(Cm, Sl, SWl);
-  mat3_vec(Cm, St, SWt);
-  mat3_mul(SWl, Rl, S.cam_L);
-  mat3_vec(SWl, Rt, tmp);
-  for (int i = 0; i < 3; ++i) S.cam_t[i] = tmp[i] + SWt[i];
-  S.cam_pos[0] = pos.x;
-  S.cam_pos[1] = pos.y;
-  S.cam_pos[2] = pos.z;
+  camera_derive(cp.position, cp.look, cp.up, cp.vfov_deg, W, H, S.cam_L, S.cam_t, S.cam_pos);
   S.imaging_ratio = cp.imaging_ratio;
 
   for (int i = 0; i < 3; ++i) {
@@ -187,6 +220,14 @@ int build_scene(const vpt_configuration& cfg, DevScene& S) {
 }
 
 }  // namespace vpt
+
+extern "C" int vpt_shutter_entry(const vpt_shutter_camera* cam, uint32_t width, uint32_t height, float* out16) {
+  if (!cam || !out16 || !width || !height) return vpt::set_error(VPT_E_INVALID, "vpt_shutter_entry: null or zero argument");
+  if (const char* why = vpt::camera_invalid(cam->position, cam->look, cam->up, cam->vfov_deg))
+    return vpt::set_error(VPT_E_INVALID, std::string("vpt_shutter_entry: ") + why);
+  vpt::shutter_entry(*cam, width, height, out16);
+  return VPT_OK;
+}
 
 extern "C" int vpt_blackbody_table(float* out) {
   if (!out) return vpt::set_error(VPT_E_INVALID, "vpt_blackbody_table: null output");

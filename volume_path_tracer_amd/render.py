@@ -265,6 +265,24 @@ class Integrator:
                    "vpt_gpu_set_light_groups")
         self._groups = groups
 
+    def set_shutter(self, cameras) -> None:
+        """Attach a shutter (vpt_gpu_set_shutter): a list of 1 .. 65536 cameras, each a dict of the keywords set_camera
+        takes (position, look, up, vfov_deg; an absent key keeps the scene's value); None or an empty list detaches.
+        While attached, wave w of render_jobs / render_waves, render_tiles and render_tile_list -- so render_uniform and
+        render_adaptive's rounds driver too -- generates its primary rays through camera (w - 1) % len(cameras) (waves
+        are 1-based here); no random draw changes.  scenes.shutter_cameras makes the list for a camera move.
+        Synchronous.  A camera that is not one (look == position, ...) raises and leaves the previous shutter."""
+        from .scenes import shutter_entries
+
+        arr = shutter_entries(self.cfg, cameras) if cameras else None
+        capi.check(capi.lib().vpt_gpu_set_shutter(self.h, arr, len(arr) if arr is not None else 0), "vpt_gpu_set_shutter")
+
+    def shutter_info(self) -> int:
+        """The number of cameras of the attached shutter, 0 if none."""
+        n = C.c_uint32()
+        capi.check(capi.lib().vpt_gpu_shutter_info(self.h, C.byref(n)), "vpt_gpu_shutter_info")
+        return int(n.value)
+
     def relight(self, groups, gains, stream=None):
         """The relit film [H][W][4] of group planes `groups` ([3][H][W][4]) under `gains` (3 x 3, [group][XYZ]; see
         scenes.light_gains): out.c = ((G0.c k0.c) + (G1.c k1.c)) + (G2.c k2.c), out.w = G0.w, by one small kernel
@@ -692,6 +710,8 @@ def render_adaptive(it: Integrator, target_error: float, min_waves: int = 64, st
     torch = it.torch
     if groups and fused:
         raise ValueError("render_adaptive: light groups are rendered by the rounds driver only (fused=False)")
+    if fused and hasattr(capi.lib(), "vpt_gpu_shutter_info") and it.shutter_info():  # (older builds in A/B runs lack it)
+        raise ValueError("render_adaptive: a shutter is attached and the fused driver does not honour it (fused=False)")
     T = it.cfg.jobs_per_wave()
     film = torch.zeros_like(it.film)
     gp = torch.zeros((3, it.cfg.height, it.cfg.width, 4), dtype=torch.float32, device=it.dev) if groups else None

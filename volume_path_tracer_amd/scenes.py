@@ -42,11 +42,12 @@ def scene(name: str) -> capi.Configuration:
     return read_configuration(SCENE_DIR / f"{name}.json")
 
 
-def orbit(cfg: capi.Configuration, frames: int, degrees: float = 360.0) -> list:
+def orbit(cfg: capi.Configuration, frames: int, degrees: float = 360.0, closing: bool = False) -> list:
     """A turntable: `frames` configurations, frame k with the camera position rotated by degrees * k / frames about the
     axis through `look` along the normalised `up` (right-handed); look, up, vfov and everything else are cfg's.
     Frame 0 is cfg's camera bit for bit, and a full turn does not repeat it at the end (frame `frames` would).  The
-    rotation is computed in float64 and rounded once to the configuration's floats."""
+    rotation is computed in float64 and rounded once to the configuration's floats.  closing: the rotation at index
+    `frames` is appended (frames + 1 configurations): where the last frame's shutter closes (--shutter)."""
     import numpy as np
 
     frames = int(frames)
@@ -59,7 +60,7 @@ def orbit(cfg: capi.Configuration, frames: int, degrees: float = 360.0) -> list:
         raise ValueError("orbit: the camera's up vector has no direction")
     axis, r = up / n, pos - look
     out = []
-    for k in range(frames):
+    for k in range(frames + 1 if closing else frames):
         c = cfg.copy()
         a = np.radians(float(degrees) * k / frames)
         if a != 0.0:  # Rodrigues' rotation of the offset from `look`
@@ -123,25 +124,35 @@ def read_camera_path(path) -> list:
         data = json.load(f)
     if not isinstance(data, list) or not data:
         raise ValueError(f"{path}: a camera path is a non-empty JSON list of cameras")
-    out = []
-    for i, cam in enumerate(data):
-        if not isinstance(cam, dict):
-            raise ValueError(f"{path}: frame {i}: a camera is an object")
-        for k in cam:
-            if k not in _CAMERA_KEYS:
-                raise ValueError(f"{path}: frame {i}: unknown key {k!r}")
-        for k in ("position", "look"):
-            if k not in cam:
-                raise ValueError(f"{path}: frame {i}: missing key {k!r}")
-        d = {}
-        for k, v in cam.items():
-            vals = v if _CAMERA_KEYS[k] == 3 else [v]
-            if (not isinstance(vals, list) or len(vals) != _CAMERA_KEYS[k]
-                    or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in vals)):
-                raise ValueError(f"{path}: frame {i}: {k!r} wants {_CAMERA_KEYS[k]} number(s)")
-            d[k] = [float(x) for x in vals] if _CAMERA_KEYS[k] == 3 else float(v)
-        out.append(d)
-    return out
+    return [_camera_entry(cam, f"{path}: frame {i}") for i, cam in enumerate(data)]
+
+
+def _camera_entry(cam, where: str) -> dict:
+    """One camera object of a camera path (or --shutter-camera's file), checked as read_camera_path states."""
+    if not isinstance(cam, dict):
+        raise ValueError(f"{where}: a camera is an object")
+    for k in cam:
+        if k not in _CAMERA_KEYS:
+            raise ValueError(f"{where}: unknown key {k!r}")
+    for k in ("position", "look"):
+        if k not in cam:
+            raise ValueError(f"{where}: missing key {k!r}")
+    d = {}
+    for k, v in cam.items():
+        vals = v if _CAMERA_KEYS[k] == 3 else [v]
+        if (not isinstance(vals, list) or len(vals) != _CAMERA_KEYS[k]
+                or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in vals)):
+            raise ValueError(f"{where}: {k!r} wants {_CAMERA_KEYS[k]} number(s)")
+        d[k] = [float(x) for x in vals] if _CAMERA_KEYS[k] == 3 else float(v)
+    return d
+
+
+def read_camera(path) -> dict:
+    """One camera: a JSON object in the keys and with the strictness of a read_camera_path entry (--shutter-camera)."""
+    import json
+
+    with open(path, "r", encoding="utf-8") as f:
+        return _camera_entry(json.load(f), str(path))
 
 
 def with_camera(cfg: capi.Configuration, position=None, look=None, up=None, vfov_deg=None) -> capi.Configuration:
@@ -154,6 +165,76 @@ def with_camera(cfg: capi.Configuration, position=None, look=None, up=None, vfov
     if vfov_deg is not None:
         cp.vfov_deg = float(vfov_deg)
     return c
+
+
+def camera_of(cfg: capi.Configuration) -> dict:
+    """cfg's camera as the dict with_camera and Integrator.set_camera take as keywords (floats as the configuration
+    holds them)."""
+    cp = cfg.camera_parameters
+    return {"position": [float(v) for v in cp.position], "look": [float(v) for v in cp.look],
+            "up": [float(v) for v in cp.up], "vfov_deg": float(cp.vfov_deg)}
+
+
+def shutter_times(n: int) -> list:
+    """The times in (0, 1) at which a shutter of n cameras samples the camera's move, in van der Corput order:
+    t_k = radical_inverse_2(k) + 2^-(m + 1), 2^m the smallest power of two >= n.  Every prefix of 2^j times has one
+    time in each interval of width 2^-j, so a tile that adaptive sampling stops after a few waves has still seen the
+    whole shutter, not its first part.  Exact in float64 (dyadic rationals)."""
+    n = int(n)
+    if not 1 <= n <= capi.VPT_SHUTTER_MAX:
+        raise ValueError(f"shutter_times: 1 .. {capi.VPT_SHUTTER_MAX} cameras")
+    m = (n - 1).bit_length()
+    out = []
+    for k in range(n):
+        r, f, i = 0.0, 0.5, k
+        while i:
+            if i & 1:
+                r += f
+            f *= 0.5
+            i >>= 1
+        out.append(r + 2.0 ** -(m + 1))
+    return out
+
+
+def lerp_camera(cam_open: dict, cam_close: dict, t: float) -> dict:
+    """The camera at time t of the move from cam_open (t = 0) to cam_close (t = 1): every field a + (b - a) t in
+    float64, rounded once to float32; t = 0 and t = 1 return the inputs' floats bit for bit.  Both are dicts of all
+    four camera keys (camera_of)."""
+    import numpy as np
+
+    out = {}
+    for k, n in _CAMERA_KEYS.items():
+        if k not in cam_open or k not in cam_close:
+            raise ValueError(f"lerp_camera: both cameras need {k!r} (camera_of(cfg) has every key)")
+        a = np.asarray(cam_open[k], np.float64).reshape(n)
+        b = np.asarray(cam_close[k], np.float64).reshape(n)
+        v = a if t == 0.0 else b if t == 1.0 else a + (b - a) * float(t)
+        v = [float(x) for x in v.astype(np.float32)]
+        out[k] = v if n == 3 else v[0]
+    return out
+
+
+def shutter_cameras(cam_open: dict, cam_close: dict, n: int, times=None) -> list:
+    """The n cameras of a shutter that opens on cam_open and closes on cam_close (Integrator.set_shutter's list):
+    lerp_camera at shutter_times(n) (or at `times`)."""
+    ts = shutter_times(n) if times is None else list(times)
+    return [lerp_camera(cam_open, cam_close, t) for t in ts]
+
+
+def shutter_entries(cfg: capi.Configuration, cameras):
+    """cameras (dicts of set_camera's keywords; an absent key keeps cfg's value) as the ctypes array
+    vpt_gpu_set_shutter takes."""
+    cams = list(cameras)
+    if not 1 <= len(cams) <= capi.VPT_SHUTTER_MAX:
+        raise ValueError(f"a shutter holds 1 .. {capi.VPT_SHUTTER_MAX} cameras")
+    arr = (capi.ShutterCamera * len(cams))()
+    for e, cam in zip(arr, cams):
+        for k in cam:
+            if k not in _CAMERA_KEYS:
+                raise ValueError(f"shutter camera: unknown key {k!r}")
+        cp = with_camera(cfg, **cam).camera_parameters
+        e.position[:], e.look[:], e.up[:], e.vfov_deg = cp.position[:], cp.look[:], cp.up[:], cp.vfov_deg
+    return arr
 
 
 def _standin_camera(cfg: capi.Configuration, distance: float) -> None:
