@@ -450,8 +450,8 @@ typedef struct vpt_shutter_camera {
  * Launches with a shutter run the throughput kernels' Shutter instantiations (ordered launches: it needs
  * VPT_FILM_ORDERED).  Calls that cannot honour it fail with VPT_E_STATE while it is attached instead of rendering the
  * still camera: vpt_gpu_render_jobs_records, vpt_gpu_trace_jobs, the pixel RNG mode, VPT_FILM_ATOMIC, a feed's
- * launch, vpt_gpu_frame_open, vpt_gpu_render_adaptive_fused and vpt_gpu_render_alpha (its matte would be another
- * camera's).  The tile-cost pass keeps using the scene's camera: only the schedule depends on it, never a sample. */
+ * launch, vpt_gpu_frame_open, vpt_gpu_render_adaptive_fused, vpt_gpu_render_alpha and vpt_gpu_render_depth (the
+ * matte and the depth would be another camera's).  The tile-cost pass keeps using the scene's camera: only the schedule depends on it, never a sample. */
 int vpt_gpu_set_shutter(vpt_gpu_ctx* ctx, const vpt_shutter_camera* cams, uint32_t n);
 /* The attached shutter's entries, 0 if none. */
 int vpt_gpu_shutter_info(const vpt_gpu_ctx* ctx, uint32_t* n);
@@ -580,8 +580,62 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
  * VPT_E_INVALID: a null context or alpha plane, sub outside 1..8.  VPT_E_STATE while a feed of the context is
  * launched and not closed (the tile-list launch's rule: the pass must not queue behind a launch that holds the
  * device).  Out of scope: the drop-in vpt_gpu::run (the reference's film has no alpha), the multi-GPU modes,
- * per-band alpha, depth and other AOVs. */
+ * per-band alpha and other AOVs.  Depth planes: the block "Depth" below. */
 int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, float* tau_device, void* hip_stream);
+
+/* Depth.  Noise-free opacity-threshold depths, a by-product of the matte's march: for each of up to four opacities
+ * the distance from the camera before which that fraction of all primary paths has had its first real collision.
+ * The rules of vpt_gpu_render_alpha: asynchronous on `hip_stream`, takes a launch slot (vpt_gpu_sync covers it),
+ * reads the scene and the density grid only, allocates nothing beyond the tile ranks the context computes once.
+ *
+ * Levels.  `n_levels` in 1..VPT_DEPTH_MAX_LEVELS opacities 0 < a_0 < a_1 < ... < 1 (host array).  Each becomes an
+ * optical depth once, on the host: tau_k = (float)(-log1p(-(double)a_k)).  a = 1/255 is the front surface of what
+ * an 8-bit matte shows, a = 0.5 the median free-flight depth.
+ *
+ * Definition.  For one primary ray z_k is the world distance from the camera position along the unit camera
+ * direction at which the accumulated optical depth first reaches tau_k.  The optical depth accumulates over the
+ * ray's positive-majorant segments exactly as the Alpha block says: lattice pieces into their segment's sum,
+ * segment sums into the ray's.  A ray that never reaches tau_k has no z_k.  World distance is the march's
+ * index-space ray time -- measured from the camera position, not from the clip entry -- multiplied by m_scale, the
+ * factor the optical depth is multiplied by.
+ *   Piece test.  After each piece the accumulated tau is formed by the expression that forms the ray's final tau,
+ *       (sigma_t * m_scale) * ((total + sum) / 6)      total: the finished segments, sum: the running segment,
+ * the division correctly rounded, and compared with the next level: reached when tau >= tau_k.  Hence, bit for
+ * bit at sub = 1: level k is reached if and only if tau_plane >= tau_k, tau_plane being what vpt_gpu_render_alpha
+ * stores for the pixel (non-negative densities; the levels are tested in ascending order, so the reached levels
+ * are a prefix).
+ *   Bisection.  In the piece [ta, tb] where the test first passes: lo = ta, hi = tb, then 16 times
+ *       tm = lo + 0.5 (hi - lo);  h = tm - ta;  part = h * ((rho(ta) + 4 rho(ta + 0.5 h)) + rho(tm))
+ *       pass = (sigma_t * m_scale) * ((total + (sum_before_piece + part)) / 6) >= tau_k;  pass ? hi = tm : lo = tm
+ * (Simpson's rule again: exact, because the field is one cubic on the whole piece).  The upper end always passes
+ * the test under this arithmetic and is kept: z_k = hi * m_scale.  Several levels may fall into one piece; they
+ * are handled in turn, each from [ta, tb].  fp32, not contracted, only +, *, comparisons and correctly rounded
+ * division: the planes equal the host build of the same code (csrc/vpt_depth.h) bit for bit; no expf is involved.
+ *   Early stop.  A ray stops marching as soon as its last level is reached.  Every loop keeps the matte's bounds
+ * (HDDA steps per ray, pieces per segment counted before the loop, the NaN-time exit); a zero or non-finite
+ * direction is no ray.
+ *   Negative densities (a signed grid): "first reaches" is the first piece whose test passes and the bisection
+ * returns one crossing within it; the result stays deterministic and equal on host and device, but the
+ * equivalence with the tau plane need not hold.
+ *
+ * Footprint: the matte's -- `sub` in 1..8, the same raster points in row-major order, one ray with jitter off (n = 1;
+ * otherwise n = sub * sub).
+ *
+ * Outputs, device float[n_levels][H][W], caller-owned, written for every pixel (in single-pixel mode only that one):
+ *     depth[k][y][x] = (sum of z_k over the sub-rays that reached level k, in that order) / (their count),
+ *                      +0.0 when none reached
+ *     reach[k][y][x] = count / n     (reach_device may be NULL) the anti-aliased mask of "opacity at least a_k",
+ *                      which makes the mean well defined for a consumer.
+ *
+ * VPT_E_INVALID: a null context, opacity array or depth plane, sub outside 1..8, n_levels outside 1..4, an opacity
+ * not in (0, 1) (a NaN included), opacities not strictly ascending.  VPT_E_STATE while a feed of the context is
+ * launched and not closed, and while a shutter is attached (the depth would be another camera's).  Out of scope:
+ * depth under a shutter, the drop-in vpt_gpu::run and feeds, the multi-GPU modes, mean collision depth and deep
+ * output, position and motion-vector planes. */
+#define VPT_DEPTH_MAX_LEVELS 4
+int vpt_gpu_render_depth(vpt_gpu_ctx* ctx, uint32_t sub, uint32_t n_levels, const float* opacity_host,
+                         float* depth_device /* [n_levels][H][W] */, float* reach_device /* same shape, may be NULL */,
+                         void* hip_stream);
 
 /* Denoise.  A variance-guided a-trous filter over a film and its moment plane, optionally guided by up to four
  * feature planes (the matte's alpha and tau / (1 + tau) are the ones a volume has).  The film is not changed: the

@@ -1,0 +1,154 @@
+"""ctypes binding of tests/native/depth_host.cpp: the depth pass's march (csrc/vpt_depth.h, the code vpt_depth_kernel
+runs per lane) on the CPU.  Compiled with hipcc, host only, as tests/alpha_lib.py compiles alpha_host.cpp
+(tests/native/Makefile does not know it): on first use, or ahead of the tests by __graft_entry__.build()."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+from volume_path_tracer_amd.capi import Configuration, GridDesc
+
+ROOT = Path(__file__).resolve().parents[1]
+NATIVE = ROOT / "tests" / "native"
+CSRC = ROOT / "volume_path_tracer_amd" / "csrc"
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+SOURCES = [NATIVE / "depth_host.cpp", CSRC / "vpt_scene.cpp", CSRC / "vpt_grid_build.cpp", CSRC / "vpt_config.cpp"]
+# alpha_lib's float flags: no contraction, the device's semantics on the host
+FLAGS = ["-std=c++20", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "--cuda-host-only",
+         "-I" + str(ROOT / "include")]
+LIB = NATIVE / "build" / "libvpt_depth_host.so"
+BISECT_STEPS = 16  # kDepthBisectSteps (csrc/vpt_depth.h, stated in include/vpt_gpu.h)
+_L = None
+
+
+def compile_host(out: Path, extra=()) -> Path:
+    """hipcc, host only: the library (extra = ["-O2", "-shared"]) or the stand-alone program (-DDEPTH_HOST_MAIN)."""
+    out.parent.mkdir(parents=True, exist_ok=True)
+    r = subprocess.run([HIPCC, *FLAGS, *extra, "-o", str(out), *map(str, SOURCES)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return out
+
+
+def build_lib() -> Path:
+    deps = SOURCES + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "vpt_gpu.h"]
+    if not LIB.exists() or LIB.stat().st_mtime < max(p.stat().st_mtime for p in deps):
+        tmp = LIB.with_name(f"{LIB.name}.{os.getpid()}.tmp")
+        compile_host(tmp, ["-O2", "-shared"])
+        os.replace(tmp, LIB)
+    return LIB
+
+
+def lib():
+    global _L
+    if _L is None:
+        build_lib()
+        import torch  # noqa: F401  (hipcc links libamdhip64: torch's runtime first, see capi.lib())
+        L = C.CDLL(str(LIB))
+        cfgp, gp, fp, ip = C.POINTER(Configuration), C.POINTER(GridDesc), C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        L.vptd_levels.argtypes = [C.c_uint32, fp, fp]
+        L.vptd_render.argtypes = [cfgp, gp, C.c_uint32, C.c_uint32, fp, fp, fp]
+        L.vptd_tau_upto.argtypes = [cfgp, gp, ip, ip, fp, C.c_uint64, fp]
+        _L = L
+    return _L
+
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def levels(opacity):
+    """tau_k float32 [K] as the library computes them: (float)(-log1p(-(double)a_k))."""
+    op = np.ascontiguousarray(opacity, np.float32).ravel()
+    tau = np.zeros(op.size, np.float32)
+    rc = lib().vptd_levels(op.size, _fp(op), _fp(tau))
+    assert rc == 0, rc
+    return tau
+
+
+def render(cfg, density, opacity, sub=1, fill=0.0):
+    """(depth, reach) float32 [K][H][W] of the frame; `fill` is what the planes hold before the call."""
+    op = np.ascontiguousarray(opacity, np.float32).ravel()
+    depth = np.full((op.size, cfg.height, cfg.width), fill, np.float32)
+    reach = np.full((op.size, cfg.height, cfg.width), fill, np.float32)
+    rc = lib().vptd_render(C.byref(cfg), C.byref(density.desc), int(sub), op.size, _fp(op), _fp(depth), _fp(reach))
+    assert rc == 0, rc
+    return depth, reach
+
+
+def tau_upto(cfg, density, x, y, z):
+    """Optical depths float32 [n] of the centre rays of the pixels (x[i], y[i]) up to the world distances z[i]."""
+    x, y = np.ascontiguousarray(x, np.int32).ravel(), np.ascontiguousarray(y, np.int32).ravel()
+    z = np.ascontiguousarray(z, np.float32).ravel()
+    assert x.shape == y.shape == z.shape
+    tau = np.zeros(z.size, np.float32)
+    ip = C.POINTER(C.c_int32)
+    rc = lib().vptd_tau_upto(C.byref(cfg), C.byref(density.desc), x.ctypes.data_as(ip), y.ctypes.data_as(ip), _fp(z),
+                             z.size, _fp(tau))
+    assert rc == 0, rc
+    return tau
+
+
+def first_real_collisions(ev, cfg):
+    """From an event log (capi.EVENT_DTYPE records in job order: the oracle's or Integrator.trace_jobs') the distance
+    |point - camera position| (float64) of every sample's first real collision on its primary ray: the first
+    sampled_point before any scatter whose next event is not a null.  Returns (pixel index py * W + px, distance), one
+    row per sample that has one."""
+    from volume_path_tracer_amd import capi
+
+    SP, NULL, SCATTER = (capi.EVENT_NAMES.index(n) for n in ("sampled_point", "null", "scatter"))
+    T = cfg.jobs_per_wave()
+    tw, th = int(cfg.tile_size[0]), int(cfg.tile_size[1])
+    ntx = -(-cfg.width // tw)
+    jid, pix, typ = ev["jid"].astype(np.int64), ev["pixel"].astype(np.int64), ev["type"]
+    key = jid * (tw * th) + pix
+    first = np.r_[True, key[1:] != key[:-1]]          # a sample's events are contiguous
+    start = np.maximum.accumulate(np.where(first, np.arange(len(ev)), 0))
+    cs = np.cumsum(typ == SCATTER)
+    primary = (cs - cs[start]) == 0
+    nxt_same = np.r_[key[1:] == key[:-1], False]
+    nxt_type = np.r_[typ[1:], NULL]
+    real = (typ == SP) & primary & nxt_same & (nxt_type != NULL)
+    pos = np.asarray(cfg.camera_parameters.position[:], np.float64)
+    dist = np.linalg.norm(ev["v"][:, :3].astype(np.float64) - pos, axis=1)
+    idx = np.flatnonzero(real)
+    _, keep = np.unique(key[idx], return_index=True)  # the first per sample (idx ascends)
+    idx = idx[keep]
+    tile = jid[idx] % T
+    x0, y0 = (tile % ntx) * tw, (tile // ntx) * th
+    rw = np.minimum(cfg.width - x0, tw)
+    px, py = x0 + pix[idx] % rw, y0 + pix[idx] // rw
+    return py * cfg.width + px, dist[idx]
+
+
+def check_first_collisions(cfg, opacity, depth, tau, pixel, dist, spp):
+    """The statistical test of the depth planes against a renderer's paths.  Per pixel and level reached: the samples
+    whose first real collision lies nearer than z_k are Binomial(spp, a_k); where a level is not reached: the samples
+    with any real collision on the primary ray are Binomial(spp, 1 - exp(-tau)), tau the matte's.  Every test's exact
+    two-sided tail above 1e-3 / tests, the pooled z-score mean within 4 / sqrt(tests)
+    (test_film_agrees_with_the_matte's forms).  No pixel is excluded.  Returns the number of tests."""
+    from scipy.stats import binom
+
+    npx = cfg.width * cfg.height
+    ks, ps = [], []
+    any_real = np.bincount(pixel, minlength=npx).astype(np.float64)
+    p_any = -np.expm1(-tau.ravel().astype(np.float64))
+    for k, a in enumerate(np.asarray(opacity, np.float32)):
+        z = depth[k].ravel().astype(np.float64)
+        reached = z > 0
+        c = np.bincount(pixel, weights=(dist < z[pixel]).astype(np.float64), minlength=npx)
+        ks.append(np.where(reached, c, any_real))
+        ps.append(np.where(reached, float(a), p_any))
+    k, p = np.concatenate(ks), np.concatenate(ps)
+    assert (k <= spp).all()
+    p_two = np.minimum(1.0, 2 * np.minimum(binom.cdf(k, spp, p), binom.sf(k - 1, spp, p)))
+    worst = p_two.argmin()
+    assert p_two.min() > 1e-3 / k.size, (p_two.min(), k[worst], p[worst], worst)
+    mid = (p > 0) & (p < 1)
+    zs = (k[mid] / spp - p[mid]) / np.sqrt(p[mid] * (1 - p[mid]) / spp)
+    print("first collisions: tests", k.size, "min tail", p_two.min(), "z mean", zs.mean(), "of", zs.size)
+    assert abs(zs.mean()) < 4.0 / np.sqrt(zs.size), (zs.mean(), zs.size)
+    return k.size

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Register / scratch / occupancy summary of the integrator kernels (gfx950), plus the .s for reading.
+# Register / scratch / occupancy summary of every kernel of the library (gfx950), plus the .s for reading.
 # Usage: tools/isa_stats.sh [extra hipcc flags...]   -> /tmp/isa/vpt.s
 mkdir -p /tmp/isa
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -7,10 +7,12 @@ R=$(cd "$(dirname "$0")/.." && pwd)
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -I"$R/volume_path_tracer_amd/csrc" \
   --cuda-device-only -S -o /tmp/isa/vpt.s "$@" "$R/volume_path_tracer_amd/csrc/vpt_gpu.hip" 2>&1 | grep -v "unused during compilation"
 python3 - <<'PY'
-import re
+import re, subprocess
 t = open("/tmp/isa/vpt.s").read()
-for m in re.finditer(r"^(_ZN3vpt20vpt_integrate_kernelI(\w+?)EEv\w*DevScene\w*):", t, re.M):
+for m in re.finditer(r"^(_ZN3vpt\w+):\s*; @", t, re.M):
     seg = t[m.end():]
     get = lambda k: re.search(r"; %s: (\d+)" % k, seg).group(1)
-    print(m.group(2), "vgpr", get("NumVgprs"), "sgpr", get("NumSGPRsForWavesPerEU"), "scratch", get("ScratchSize"), "occ", get("Occupancy"))
+    name = subprocess.run(["c++filt", "-p", m.group(1)], capture_output=True, text=True).stdout.strip() or m.group(1)
+    print(name.replace("vpt::", ""), "vgpr", get("NumVgprs"), "sgpr", get("NumSGPRsForWavesPerEU"), "lds", get("LDSByteSize"),
+          "scratch", get("ScratchSize"), "occ", get("Occupancy"))
 PY

@@ -44,8 +44,14 @@ camera (``--frames`` with an orbit, or ``--camera-path``) ``--shutter F`` (0 < F
 by the fraction F towards frame k + 1's; the last frame of a camera path extrapolates its previous step, the last
 frame of an orbit uses the rotation at index ``frames``.  The uniform frame is then one ordered launch
 (render.render_uniform), the adaptive one the rounds driver; ``--light-groups``, ``--relight`` and ``--denoise
---denoise-no-guides`` work.  Not with ``--alpha``, ``--alpha-foreground``, ``--alpha-out``, ``--denoise`` guided by the
-matte, ``--adaptive-fused``, ``--rng-mode pixel`` or ``--event-log``: exit 1 before a device is touched.
+--denoise-no-guides`` work.  Not with ``--alpha``, ``--alpha-foreground``, ``--alpha-out``, ``--depth-out``, ``--denoise``
+guided by the matte, ``--adaptive-fused``, ``--rng-mode pixel`` or ``--event-log``: exit 1 before a device is touched.
+``--depth-out z.npy`` saves the depth planes (Integrator.render_depth; float32 [K][H][W]): per
+opacity of ``--depth-opacity A[,A...]`` (1..4 ascending values in (0, 1), default ``0.00392157,0.5``: the 8-bit matte's front
+surface and the median free-flight depth) the distance from the camera at which a pixel's optical depth first reaches
+that opacity, 0 where it never does.  ``--depth-sub N`` sets the sub-rays per axis (default 1), ``--depth-reach-out r.npy``
+saves the fraction of sub-rays that reached each level.  One deterministic pass after the frame, with every driver and in
+sequences; not with a shutter, and the other three flags need ``--depth-out``: exit 1 before a device is touched.
 ``--rng-mode pixel`` renders the plain uniform frame in the pixel RNG mode (one stream per pixel sample; not the
 reference's samples).
 Exits 1 on a fatal error, like vptFATAL.
@@ -68,6 +74,24 @@ def _parse_synth(spec: str):
 
 
 _FIELD = re.compile(r"%0?\d*d")
+_DEPTH_OPACITY = "0.00392157,0.5"
+
+
+def _parse_depth_opacity(spec: str):
+    """--depth-opacity's levels: 1..4 strictly ascending numbers in (0, 1), as float32 (what the library compares)."""
+    import numpy as np
+
+    try:
+        a = np.array([float(x) for x in spec.split(",")], dtype=np.float32)
+    except ValueError:
+        raise ValueError(f"--depth-opacity wants A[,A...], got {spec!r}") from None
+    if not 1 <= a.size <= 4:
+        raise ValueError(f"--depth-opacity wants 1..4 opacities, got {a.size}")
+    if not bool(np.all((a > 0) & (a < 1))):  # (also a NaN)
+        raise ValueError(f"--depth-opacity: every opacity lies in (0, 1), got {spec!r}")
+    if not bool(np.all(a[1:] > a[:-1])):
+        raise ValueError(f"--depth-opacity: the opacities ascend strictly, got {spec!r}")
+    return a
 _GROUPS = ("emission", "sun", "sky")
 
 
@@ -171,6 +195,12 @@ def main(argv=None) -> int:
                     help="motion blur: cameras across the shutter (default num_waves, at most 65536)")
     ap.add_argument("--shutter", type=float, default=None, metavar="F",
                     help="sequence: blur frame k by the fraction F (0 < F <= 1) of the move to frame k + 1's camera")
+    ap.add_argument("--depth-out", default=None, help="save the depth planes (.npy, float32 [K][H][W])")
+    ap.add_argument("--depth-opacity", default=None, metavar="A[,A...]",
+                    help=f"depth: 1..4 ascending opacities in (0, 1) (default {_DEPTH_OPACITY})")
+    ap.add_argument("--depth-sub", type=int, default=None, metavar="N", help="depth: N x N sub-rays per pixel, 1..8 (default 1)")
+    ap.add_argument("--depth-reach-out", default=None,
+                    help="depth: save the fraction of sub-rays that reached each level (.npy, float32 [K][H][W])")
     ap.add_argument("--rng-mode", choices=("reference", "pixel"), default="reference",
                     help="pixel: one RNG stream per pixel sample (the plain uniform frame only)")
     args = ap.parse_args(argv)
@@ -189,10 +219,27 @@ def main(argv=None) -> int:
                 print(f"[vpt] FATAL: {flag} does not combine with --light-groups / --relight (out of scope: README, "
                       f"Light groups)", file=sys.stderr)
                 return 1
+    depth_opacity = None
+    if args.depth_out is None:
+        for flag, given in (("--depth-opacity", args.depth_opacity), ("--depth-sub", args.depth_sub),
+                            ("--depth-reach-out", args.depth_reach_out)):
+            if given is not None:
+                print(f"[vpt] FATAL: {flag} needs --depth-out", file=sys.stderr)
+                return 1
+    else:
+        try:
+            depth_opacity = _parse_depth_opacity(_DEPTH_OPACITY if args.depth_opacity is None else args.depth_opacity)
+        except ValueError as e:
+            print(f"[vpt] FATAL: {e}", file=sys.stderr)
+            return 1
+        if args.depth_sub is not None and not 1 <= args.depth_sub <= 8:
+            print("[vpt] FATAL: --depth-sub wants 1 .. 8 sub-rays per axis", file=sys.stderr)
+            return 1
     want_shutter = args.shutter_camera is not None or args.shutter is not None
     if want_shutter:  # (checked before anything touches a device: these would render the still camera, or raise late)
         for flag, on in (("--alpha", args.alpha), ("--alpha-foreground", args.alpha_foreground),
-                         ("--alpha-out", args.alpha_out), ("--denoise", args.denoise and not args.denoise_no_guides),
+                         ("--alpha-out", args.alpha_out), ("--depth-out", args.depth_out),
+                         ("--denoise", args.denoise and not args.denoise_no_guides),
                          ("--adaptive-fused", args.adaptive_fused), ("--rng-mode pixel", args.rng_mode == "pixel"),
                          ("--event-log", args.event_log), ("--relight-from", args.relight_from)):
             if on:
@@ -228,7 +275,8 @@ def main(argv=None) -> int:
     sequence = args.frames is not None or args.camera_path is not None or args.volume_sequence is not None
     outputs = {"output_path": args.output_path, "--film-out": args.film_out, "--alpha-out": args.alpha_out,
                "--waves-out": args.waves_out, "--denoised-film-out": args.denoised_film_out,
-               "--moments-out": args.moments_out, "--event-log": args.event_log, "--groups-out": args.groups_out}
+               "--moments-out": args.moments_out, "--event-log": args.event_log, "--groups-out": args.groups_out,
+               "--depth-out": args.depth_out, "--depth-reach-out": args.depth_reach_out}
     if sequence:
         problem = _sequence_problem(args, outputs)
         if problem:
@@ -328,6 +376,9 @@ def main(argv=None) -> int:
                 alpha = it.render_alpha(sub=args.alpha_sub)
             res["alpha"] = alpha
             emit("alpha")
+        if args.depth_out:
+            res["depth"], res["reach"] = it.render_depth(depth_opacity, sub=args.depth_sub or 1, reach=True)
+            emit("depth")
         if args.denoise:
             if args.denoise_no_guides:
                 guides = []
@@ -344,7 +395,7 @@ def main(argv=None) -> int:
         emit("png")
         return res
 
-    PIECES = ("waves", "events", "film", "groups", "alpha", "m2", "denoised", "png")
+    PIECES = ("waves", "events", "film", "groups", "alpha", "depth", "m2", "denoised", "png")
 
     def write_piece(piece, res, paths):
         """One of a frame's files, from what render_frame has produced (host work only)."""
@@ -363,6 +414,10 @@ def main(argv=None) -> int:
                 image.save_png(_group_path(paths["output_path"], name), image.film_to_image(plane))
         elif piece == "alpha" and "alpha" in res and paths["--alpha-out"]:
             np.save(paths["--alpha-out"], res["alpha"])
+        elif piece == "depth" and "depth" in res:
+            np.save(paths["--depth-out"], res["depth"])
+            if paths["--depth-reach-out"]:
+                np.save(paths["--depth-reach-out"], res["reach"])
         elif piece == "m2" and args.denoise and paths["--moments-out"]:
             np.save(paths["--moments-out"], res["m2"])
         elif piece == "denoised" and args.denoise and paths["--denoised-film-out"]:

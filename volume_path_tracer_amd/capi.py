@@ -308,6 +308,8 @@ def lib() -> C.CDLL:
         L.vpt_shutter_entry.argtypes = [C.POINTER(ShutterCamera), C.c_uint32, C.c_uint32, fp]
     if hasattr(L, "vpt_gpu_render_alpha"):  # (older builds in A/B runs lack the coverage pass)
         L.vpt_gpu_render_alpha.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    if hasattr(L, "vpt_gpu_render_depth"):  # (older builds in A/B runs lack the depth pass)
+        L.vpt_gpu_render_depth.argtypes = [vp, C.c_uint32, C.c_uint32, fp, vp, vp, vp]
     if hasattr(L, "vpt_gpu_denoise"):  # (older builds in A/B runs lack the denoiser)
         L.vpt_gpu_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, C.POINTER(vp), vp, vp, vp]
     L.vpt_gpu_sync.argtypes = [vp]

@@ -1367,6 +1367,37 @@ int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, fl
   return VPT_OK;
 }
 
+int vpt_gpu_render_depth(vpt_gpu_ctx* ctx, uint32_t sub, uint32_t n_levels, const float* opacity_host, float* depth_device,
+                         float* reach_device, void* hip_stream) {
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_depth: null context");
+  if (!depth_device) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_depth: null depth plane");
+  if (sub < 1 || sub > vpt::kAlphaMaxSub)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_depth: sub-rays per axis must be 1..8");
+  vpt::DepthLevels levels;  // (tau_k = -log1p(-a_k), once, here)
+  if (const char* why = vpt::depth_levels(n_levels, opacity_host, levels))
+    return vpt::set_error(VPT_E_INVALID, std::string("vpt_gpu_render_depth: ") + why);
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_depth: a feed of this context is open");
+  if (!ctx->shutter.empty())
+    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_depth: a shutter is attached and the depth would be the scene "
+                                       "camera's alone: detach it (vpt_gpu_set_shutter NULL, 0)");
+  if (!ctx->volume_ok) return volume_gone();
+  if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
+  const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
+  if (blocks >= (1ULL << 31)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_depth: 2^31 or more pixel chunks");
+  hipStream_t s = (hipStream_t)hip_stream;
+  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the pass as for any launch)
+  if ((rc = take_slot(ctx, s, slot))) return rc;
+  hipLaunchKernelGGL(vpt::vpt_depth_kernel, dim3((unsigned)blocks), dim3(64), 0, s, ctx->scene_dev,
+                     (const uint32_t*)ctx->order, sub, levels, depth_device, reach_device);
+  const hipError_t e = hipGetLastError();
+  if ((rc = release_slot(ctx, s, slot))) return rc;
+  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_render_depth: ") + hipGetErrorString(e));
+  return VPT_OK;
+}
+
 int vpt_gpu_denoise(vpt_gpu_ctx* ctx, const vpt_denoise_params* p, const float* film_device, const float* m2_device,
                     const float* const* guides_device, float* out_film_device, float* var_out_device, void* hip_stream) {
   // (the arguments are checked before the context, so that every refusal is testable without a device)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "vpt_alpha.h"
+#include "vpt_depth.h"
 #include "vpt_internal.h"
 #include "vpt_launch.h"
 
@@ -1413,6 +1414,35 @@ __global__ __launch_bounds__(64) void vpt_alpha_kernel(const DevScene* scene, co
   const uint64_t p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
   alpha[p] = a;
   if (tau) tau[p] = od;
+}
+
+// The depth pass (vpt_gpu_render_depth): per pixel and level the mean distance at which the optical depth of the
+// pixel's sub-rays first reaches the level, by the march of vpt_depth.h.  vpt_alpha_kernel's shape: a block is one
+// wavefront that owns up to 64 pixels of one tile, block = (tile slot, chunk of 64 pixels), lane p = pixel p of the
+// chunk, tile slot b renders tile rank[b].  The levels come by value (scalar loads, no per-lane table); a lane keeps
+// per level a sum and a count, and per ray the index of its next level.  A lane whose ray has stopped waits for its
+// wavefront's longest ray.  No LDS, no atomics, nothing shared between blocks; every pixel is written exactly once.
+__global__ __launch_bounds__(64) void vpt_depth_kernel(const DevScene* scene, const uint32_t* rank, uint32_t sub,
+                                                       DepthLevels levels, float* depth, float* reach) {
+  const DevScene& S = *scene;
+  const uint32_t area = S.tile_area, chunks = (area + 63u) / 64u;
+  const uint32_t tb = blockIdx.x / chunks, q = (blockIdx.x - tb * chunks) * 64u + threadIdx.x;
+  if ((uint64_t)tb >= S.T) return;
+  const uint32_t t = rank[tb];
+  const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
+  const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
+  if (q >= area || (int32_t)q >= rw * rh) return;
+  const int32_t yl = (int32_t)q / rw, px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
+  if (S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) return;
+  float d[kDepthMaxLevels], r[kDepthMaxLevels];
+  depth_pixel(S, px, py, sub, levels, d, r);
+  const uint64_t plane = (uint64_t)S.H * (uint64_t)S.W, p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
+#pragma unroll
+  for (uint32_t k = 0; k < kDepthMaxLevels; ++k)
+    if (k < levels.n) {
+      depth[k * plane + p] = d[k];
+      if (reach) reach[k * plane + p] = r[k];
+    }
 }
 
 }  // namespace vpt

@@ -360,6 +360,33 @@ class Integrator:
         s.synchronize()
         return (a.cpu().numpy(), t.cpu().numpy()) if tau else a.cpu().numpy()
 
+    def render_depth(self, opacity=(1.0 / 255.0, 0.5), sub=None, reach: bool = False, stream=None):
+        """The depth planes, numpy float32 [K][H][W]: per opacity a_k of `opacity` (1..4 values, 0 < a_0 < ... < 1) the
+        distance from the camera at which a pixel's optical depth first reaches -log1p(-a_k), the depth before which
+        that fraction of the primary paths has collided, by one deterministic pass (vpt_gpu_render_depth: the matte's
+        march, stopped at the last level; no noise); +0.0 where the level is not reached.  sub=None: what it means
+        for render_alpha (4 with jitter, 1 without); a pixel holds the mean over the sub-rays that reached the level.
+        reach=True: (depth, reach) with the fraction of sub-rays that did.  Synchronous; in single-pixel mode every
+        other pixel is 0.  Touches no film."""
+        torch = self.torch
+        if sub is None:
+            sub = 4 if self.cfg.worker_parameters.use_jitter else 1
+        if not 1 <= int(sub) <= 8:
+            raise ValueError("render_depth: sub is 1..8 sub-rays per axis")
+        op = np.ascontiguousarray(np.atleast_1d(np.asarray(opacity, dtype=np.float32)))
+        if op.ndim != 1 or not 1 <= op.size <= 4:
+            raise ValueError("render_depth: 1..4 opacity levels")
+        shape = (int(op.size), self.cfg.height, self.cfg.width)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        with torch.cuda.stream(s):  # (the zero fills run on the pass's stream, ahead of it)
+            d = torch.zeros(shape, dtype=torch.float32, device=self.dev)
+            r = torch.zeros(shape, dtype=torch.float32, device=self.dev) if reach else None
+        capi.check(capi.lib().vpt_gpu_render_depth(self.h, int(sub), int(op.size), op.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   C.c_void_p(d.data_ptr()), C.c_void_p(r.data_ptr()) if reach else None,
+                                                   C.c_void_p(int(s.cuda_stream))), "vpt_gpu_render_depth")
+        s.synchronize()
+        return (d.cpu().numpy(), r.cpu().numpy()) if reach else d.cpu().numpy()
+
     def denoise(self, film, m2, guides=(), guide_sigma=None, iterations: int = 4, sigma_l: float = 4.0,
                 rel_floor: float = 1e-3, variance: bool = False, stream=None):
         """The denoised film of `film` ([H][W][4]) and its moment plane `m2` ([H][W]): the variance-guided a-trous
