@@ -5,9 +5,10 @@ priority 3, so its region is the one after `s_setprio 3`).
     hipcc -xhip --offload-arch=gfx950 --cuda-device-only -S <build.py's flags> volume_path_tracer_amd/csrc/vpt_gpu.hip -o /tmp/vpt.s
     python tools/isa_blocks.py /tmp/vpt.s [flags ...]
 
-flags: the kernel's template bools HasTemp, Debug, Runs, Lat, Compact, Feed as a digit string (default: every
-kernel; e.g. 000000 = the density kernel C3 runs, 001000 = its run-skipping variant, 100000 = the temperature
-kernel C4 runs)."""
+flags: the kernel's template bools HasTemp, Debug, Runs, Lat, Compact, Feed, Band, Gang, Groups, Shutter as a digit
+string (default: every kernel; e.g. 0000000000 = the density kernel C3 runs, 0010000000 = its run-skipping variant,
+1000000000 = the temperature kernel C4 runs, 0000001010 = the density kernel of a band launch with light groups;
+csrc/vpt_variant.h variant_valid says which of the 1 024 strings exist)."""
 import re
 import sys
 

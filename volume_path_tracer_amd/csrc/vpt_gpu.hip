@@ -1,8 +1,10 @@
 // vpt_gpu.hip — the integrator context and the C ABI around the kernels (include/vpt_gpu.h): grid upload,
-// scene constants, the launch choices of render() (kernel variant, grid size, job order, the ordered film's
-// sample buffer and film pass), counters and knobs.  The device code is vpt_kernels.h (included here, the one
-// translation unit that launches it); the feeds' host protocol is vpt_feed.cpp; the state both share is
-// vpt_ctx.h.
+// scene constants, render() (its checks, the ordered film's sample buffer and film passes), counters and knobs.
+// The launch choices of render() -- kernel variant, grid size, gate set, job order -- are plan_launch's, and the
+// rule for which kernel variants exist is variant_valid's (both vpt_variant.h; DESIGN.md "Kernel variants and the
+// launch plan"); integrate_kernel() here is the one table of instantiations.  The device code is vpt_kernels.h
+// (included here, the one translation unit that launches it); the feeds' host protocol is vpt_feed.cpp; the state
+// both share is vpt_ctx.h.
 //
 // Kernel shape: a persistent grid sized to the device's resident capacity.  Every lane runs the state machine
 // of vpt_integrator.h; when its (tile, wave) job ends it takes the next job id from a device counter, so lanes
@@ -13,6 +15,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +28,7 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "vpt_ctx.h"
@@ -138,8 +142,6 @@ namespace {
 
 constexpr int kProfWords = 2 * vpt::PB_COUNT + vpt::PT_COUNT;
 constexpr uint32_t kLaunchSlots = 64;
-// Latency-bound launches: at most this many work items per wavefront of the grid (see render()).
-constexpr uint64_t kSpreadLanes = 6;
 
 int wait_ctx(vpt_gpu_ctx* ctx);
 
@@ -438,6 +440,182 @@ int default_pool_policy() {
   return VPT_POOL_AUTO;
 }
 
+// The integrate kernel of a variant, or null where variant_valid says there is none: a table over the 1 024 flag
+// combinations, built at compile time.  Entry i's template arguments and its validity test read the one decoded
+// value, so an entry cannot name another variant's kernel, and the valid entries are the library's instantiations.
+using IntegrateKernel = void (*)(vpt::KernelArgs, const vpt::DevScene*, unsigned long long*);
+template <uint32_t I>
+constexpr IntegrateKernel integrate_entry() {
+  constexpr vpt::KernelVariant v = vpt::variant_decode(I);
+  if constexpr (vpt::variant_valid(v))
+    return &vpt::vpt_integrate_kernel<v.temp, v.debug, v.runs, v.lat, v.compact, v.feed, v.band, v.gang, v.groups, v.shutter>;
+  else
+    return nullptr;
+}
+template <uint32_t... I>
+constexpr std::array<IntegrateKernel, sizeof...(I)> integrate_table(std::integer_sequence<uint32_t, I...>) {
+  return {integrate_entry<I>()...};
+}
+IntegrateKernel integrate_kernel(const vpt::KernelVariant& v) {
+  static constexpr auto table = integrate_table(std::make_integer_sequence<uint32_t, vpt::kVariantCount>());
+  return table[vpt::variant_index(v)];
+}
+static_assert(vpt::kPlanOrderGroup == vpt::kOrderGroup, "the launch plan's default group is the integrator's");
+
+// Launches the integrate kernel of `v`: the one place that records which gate set and evaluation the launch ran with
+// (vpt_gpu_gate_info) and checks the launch.
+int launch_integrate(vpt_gpu_ctx* ctx, const vpt::KernelVariant& v, uint32_t blocks, size_t shmem, hipStream_t s,
+                     const vpt::KernelArgs& args, const vpt::DevScene* scene) {
+  const IntegrateKernel kernel = integrate_kernel(v);
+  if (!kernel) return vpt::set_error(VPT_E_INVALID, "launch: no integrate kernel of variant " + std::to_string(vpt::variant_index(v)));
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), shmem, s, args, scene, ctx->counters);
+  ctx->last_gate_set = scene == ctx->scene_full_dev ? VPT_GATES_FULL
+                       : scene == ctx->scene_lat_dev ? VPT_GATES_LATENCY : VPT_GATES_CONTEXT;  // (vpt_gpu_gate_info)
+  // (the instantiation just launched splits the evaluation: a density-only production launch of a throughput kernel)
+  ctx->last_eval_split = vpt::variant_eval_split(v) ? 1 : 0;
+  VPT_HIP(hipGetLastError());
+  return VPT_OK;
+}
+
+// What plan_launch reads of a render() call.
+vpt::LaunchInputs launch_inputs(const vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, const float* records,
+                                const vpt_event* events, const vpt::FeedLaunch* feed, const vpt::BandLaunch* band) {
+  vpt::LaunchInputs in;
+  in.jid_begin = jid_begin;
+  in.jid_count = jid_count;
+  in.T = ctx->scene.T;
+  in.tile_area = ctx->scene.tile_area;
+  in.grid_blocks = ctx->grid_blocks;
+  in.grid_user = ctx->grid_user;
+  in.cus = ctx->cus;
+  in.lat_per_cu = ctx->lat_per_cu;
+  in.lat_mode = ctx->lat_mode;
+  in.lat_ungated = ctx->lat_ungated;
+  in.compact_every = ctx->compact_every;
+  in.compact_per_cu = ctx->compact_per_cu;
+  in.has_temperature = ctx->scene.has_temperature != 0;
+  in.use_runs = ctx->use_runs;
+  in.pixel_mode = ctx->scene.pixel_mode != 0;
+  in.pixel_chunk = ctx->pixel_chunk;
+  in.order_mode = ctx->order_mode;
+  in.order_tail_waves = ctx->order_tail_waves;
+  in.film_order = ctx->film_order;
+  in.frame_waves = ctx->frame_waves;
+  in.records = records != nullptr;
+  in.events = events != nullptr;
+  in.feed = feed != nullptr;
+  in.band = band != nullptr;
+  in.groups = ctx->groups != nullptr;
+  in.shutter = !ctx->shutter.empty();
+  in.moments = ctx->m2 != nullptr;
+  return in;
+}
+
+// What only an ordered launch with a sample buffer honours -- the moment plane, the light groups, the shutter, in the
+// order they are reported -- and the two refusals each of them makes (vpt_variant.h attachments_refuse has the why).
+struct Attachments {
+  struct One {
+    bool on;
+    const char *subject, *cannot, *detach;
+  } a[3];
+  explicit Attachments(const vpt::LaunchInputs& in)
+      : a{{in.moments && !in.feed, "a moment plane is", "would add with film atomics", "it (vpt_gpu_set_film_moments NULL)"},
+          {vpt::launch_groups(in), "light groups are", "would add with film atomics", "them (vpt_gpu_set_light_groups NULL)"},
+          {in.shutter, "a shutter is", "cannot honour it", "it (vpt_gpu_set_shutter NULL, 0)"}} {}
+  const One* first() const {
+    for (const One& x : a)
+      if (x.on) return &x;
+    return nullptr;
+  }
+  // The launch is no ordered one, or a frame is open.
+  int refuse(const vpt::LaunchInputs& in) const {
+    const One& x = *first();
+    const char* const open_or_debug = in.frame_waves ? "a frame is open" : in.records || in.events ? "a debug launch" : nullptr;
+    const char* const why = &x != &a[2]   ? (open_or_debug ? open_or_debug : "not an ordered launch of the reference RNG mode")
+                            : in.feed     ? "a feed's launch"
+                            : open_or_debug ? open_or_debug
+                            : in.pixel_mode ? "the pixel RNG mode"
+                                            : "VPT_FILM_ATOMIC";
+    return vpt::set_error(VPT_E_STATE, std::string("render: ") + x.subject + " attached and this launch " + x.cannot + " (" +
+                                           why + "): detach " + x.detach);
+  }
+  // The launch got no sample buffer.
+  int refuse_grow() const {
+    return vpt::set_error(VPT_E_STATE, std::string("render: ") + first()->subject +
+                                           " attached and the sample buffer would have to grow while a feed of the context "
+                                           "is open (the launch would add with film atomics)");
+  }
+};
+
+// A band launch's tile ranks and its arguments.  The whole frame's ranks are the job order itself; another band's are
+// filtered from it on the launch's stream -- after the wait for the sample buffer's previous launch, so after the previous
+// band launch has read the buffer -- unless the buffer still holds this band's.
+int band_ranks(vpt_gpu_ctx* ctx, const vpt::BandLaunch& band, hipStream_t s, vpt::KernelArgs& env) {
+  const uint64_t T = ctx->scene.T;
+  env.band_rank = ctx->order;
+  env.band_slot_map = nullptr;
+  if (band.list) {
+    // a tile list (uploaded by vpt_gpu_render_tile_list): its ranks are filtered by the slot map, once per list
+    if (!ctx->band_rank || !ctx->list_dev || !ctx->list_slot_dev)
+      return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tile_list: no tile-list buffers (their allocation failed)");
+    if (!ctx->list_ranked) {
+      hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, 0u, band.tiles,
+                         ctx->band_rank, ctx->list_slot_dev);
+      VPT_HIP(hipGetLastError());
+      ctx->band_rank_lo = ctx->band_rank_hi = 0;  // (no longer a band's)
+      ctx->list_ranked = true;
+    }
+    env.band_rank = ctx->band_rank;
+    env.band_slot_map = ctx->list_slot_dev;
+  } else if (band.tile_lo != 0 || band.tiles != T) {
+    if (!ctx->band_rank) return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tiles: no tile-rank buffer (its allocation failed)");
+    if (ctx->band_rank_lo != band.tile_lo || ctx->band_rank_hi != band.tile_lo + band.tiles) {
+      hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, band.tile_lo,
+                         band.tile_lo + band.tiles, ctx->band_rank, (const uint32_t*)nullptr);
+      VPT_HIP(hipGetLastError());
+      ctx->band_rank_lo = band.tile_lo;
+      ctx->band_rank_hi = band.tile_lo + band.tiles;
+      ctx->list_ranked = false;
+    }
+    env.band_rank = ctx->band_rank;
+  }
+  env.band_waves = band.waves;
+  env.band_T = (uint32_t)T;
+  env.band_tile_lo = band.tile_lo;
+  env.band_groups = vpt::band_groups(band.waves, band.group);
+  env.band_group = band.group;
+  return VPT_OK;
+}
+
+// The ordered film's passes over a launch's sample buffer: the film -- a band's pixels, or the frame's pixel by pixel --
+// in wave order (sample counts and the moment plane included), then with light groups the same pass over each group's
+// region into its plane (w += 1, xyz += imaging_ratio * Lg, in wave order).
+int film_passes(vpt_gpu_ctx* ctx, const vpt::KernelArgs& env, const vpt::BandLaunch* band, bool groups, uint64_t jid_begin,
+                uint64_t jid_count, hipStream_t s) {
+  auto pass = [&](float* film, const float* samples, float* m2) {
+    if (band) {
+      const uint32_t chunks = (ctx->scene.tile_area + 63u) / 64u;
+      const uint32_t* const list = band->list ? ctx->list_dev : nullptr;
+      hipLaunchKernelGGL(m2 ? vpt::vpt_band_order_kernel<true> : vpt::vpt_band_order_kernel<false>,
+                         dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev, film, samples, band->tile_lo,
+                         band->waves, env.band_groups, band->group, list, m2);
+    } else {
+      const uint64_t threads = ctx->scene.T * (uint64_t)ctx->scene.tile_area;
+      hipLaunchKernelGGL(m2 ? vpt::vpt_film_order_kernel<true> : vpt::vpt_film_order_kernel<false>,
+                         dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ctx->scene_dev, film, samples, jid_begin,
+                         jid_count, m2);
+    }
+    return hipGetLastError();
+  };
+  const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
+  VPT_HIP(pass(env.film, env.samples, ctx->m2));
+  for (uint64_t g = 0; groups && g < 3; ++g)
+    VPT_HIP(pass(ctx->groups + g * npix * 4, env.samples + (g + 1) * env.group_stride, nullptr));
+  VPT_HIP(hipEventRecord(ctx->samples_done, s));
+  ctx->samples_used = true;
+  return VPT_OK;
+}
+
 }  // namespace
 
 int vpt::host::ctx_device(vpt_gpu_ctx* ctx) {
@@ -457,6 +635,7 @@ int vpt::host::launch_tile_counts(vpt_gpu_ctx* ctx, float* film, const uint32_t*
 int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, float* film, float* records,
                       void* stream_ptr, vpt_event* events, uint64_t event_cap, uint32_t* slot_out,
                       const vpt::FeedLaunch* feed, const vpt::BandLaunch* band) {
+  // 1. the arguments and the attachments
   if (!ctx) return vpt::set_error(VPT_E_INVALID, "render: null context");
   int rc = ctx_device(ctx);
   if (rc) return rc;
@@ -466,162 +645,45 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
     return vpt::set_error(VPT_E_INVALID, "render: feeds run the reference RNG mode's production kernels only");
   if (band && (feed || records || events || ctx->scene.pixel_mode || ctx->film_order != VPT_FILM_ORDERED || ctx->frame_waves))
     return vpt::set_error(VPT_E_INVALID, "render: band launches are ordered production launches of the reference RNG mode");
-  // The ordered film: production launches of the reference RNG mode (debug launches and feeds add atomically).
+  const vpt::LaunchInputs in = launch_inputs(ctx, jid_begin, jid_count, records, events, feed, band);
+  const Attachments attached(in);
+  if (vpt::attachments_refuse(in)) return attached.refuse(in);
+  // 2. The ordered film: production launches of the reference RNG mode (debug launches and feeds add atomically).
   // A launch whose sample buffer would exceed the cap is rendered as consecutive launches (whole waves where it
   // can); each adds its own waves in order, so the film is the same.
   // Light groups (vpt_gpu_set_light_groups): four regions of the sample layout instead of one (kGroupRegions).
-  const bool groups = ctx->groups != nullptr && !feed;
+  const bool groups = vpt::launch_groups(in);
   const uint64_t per_job = (uint64_t)ctx->scene.tile_area * 3 * sizeof(float) * (groups ? vpt::kGroupRegions : 1);
-  const bool ordered = ctx->film_order == VPT_FILM_ORDERED && !feed && !records && !events && !ctx->scene.pixel_mode;
-  // The moment plane (vpt_gpu_set_film_moments) is written by the ordered film passes only: a launch that would add
-  // with film atomics fails instead of leaving the plane behind the film.  (Feeds never write it.)
-  if (ctx->m2 && !feed && (!ordered || ctx->frame_waves))
-    return vpt::set_error(VPT_E_STATE, "render: a moment plane is attached and this launch would add with film atomics (" +
-                                           std::string(ctx->frame_waves ? "a frame is open"
-                                                       : records || events ? "a debug launch"
-                                                                           : "not an ordered launch of the reference RNG mode") +
-                                           "): detach it (vpt_gpu_set_film_moments NULL)");
-  // The light-group planes likewise: written by the ordered film passes only.
-  if (groups && (!ordered || ctx->frame_waves))
-    return vpt::set_error(VPT_E_STATE, "render: light groups are attached and this launch would add with film atomics (" +
-                                           std::string(ctx->frame_waves ? "a frame is open"
-                                                       : records || events ? "a debug launch"
-                                                                           : "not an ordered launch of the reference RNG mode") +
-                                           "): detach them (vpt_gpu_set_light_groups NULL)");
-  // The shutter (vpt_gpu_set_shutter): honoured by the ordered production launches' Shutter kernels only; any other
-  // launch fails instead of rendering the still camera.
-  const bool shutter = !ctx->shutter.empty();
-  if (shutter && (feed || !ordered || ctx->frame_waves))
-    return vpt::set_error(VPT_E_STATE, "render: a shutter is attached and this launch cannot honour it (" +
-                                           std::string(feed ? "a feed's launch"
-                                                       : ctx->frame_waves ? "a frame is open"
-                                                       : records || events ? "a debug launch"
-                                                       : ctx->scene.pixel_mode ? "the pixel RNG mode"
-                                                                               : "VPT_FILM_ATOMIC") +
-                                           "): detach it (vpt_gpu_set_shutter NULL, 0)");
-  if (ordered && !band) {  // (vpt_gpu_render_tiles splits its launches itself: by waves)
+  const uint64_t T = ctx->scene.T;
+  if (vpt::launch_ordered(in) && !band) {  // (vpt_gpu_render_tiles splits its launches itself: by waves)
     const uint64_t max_jobs = std::min<uint64_t>(ordered_cap(ctx, jid_count * per_job) / per_job, 0xffffffffULL);
     if (max_jobs == 0) return vpt::set_error(VPT_E_NOMEM, "ordered film: no room for one job's samples");
     if (jid_count > max_jobs) {
-      const uint64_t T = ctx->scene.T;
       const uint64_t chunk = max_jobs >= T ? max_jobs / T * T : max_jobs;
       for (uint64_t b = 0; b < jid_count; b += chunk)
         if ((rc = render(ctx, jid_begin + b, std::min(chunk, jid_count - b), film, nullptr, stream_ptr))) return rc;
       return VPT_OK;
     }
   }
-  const uint64_t total = ctx->scene.T * (uint64_t)ctx->cfg.num_waves;
-  (void)total;  // jids beyond num_waves are valid jobs too (TileProvider only stops at requested_waves)
+  if (in.pixel_mode && jid_count > UINT64_MAX / in.tile_area) return vpt::set_error(VPT_E_INVALID, "render: job range too large");
+  // 3. the launch's decisions (vpt_variant.h)
+  const vpt::LaunchPlan plan = vpt::plan_launch(in);
+  // 4. the buffers and the kernel's arguments
   hipStream_t s = (hipStream_t)stream_ptr;  // NULL = the null stream (HIP convention)
   vpt::KernelArgs env{};
   env.jid_begin = jid_begin;
-  env.jid_count = jid_count;
-  env.pixel_chunk = 1;
-  if (ctx->scene.pixel_mode) {  // work items are chunks of pixel_chunk pixels of one job
-    const uint64_t area = ctx->scene.tile_area;
-    if (jid_count > UINT64_MAX / area) return vpt::set_error(VPT_E_INVALID, "render: job range too large");
-    const uint64_t items = jid_count * area;
-    // One work item per pixel makes every pixel a device-wide atomic on the launch's job counter, and a
-    // wavefront's fetches then serialise there (C3: 530 M pixels, 546 ms vs 348 in the reference mode,
-    // r03zf).  Pixels are taken pixel_chunk at a time: the largest power of two dividing the tile area that
-    // still leaves >= 32 chunks per resident lane (C3 / C5: 32 pixels; C2, C1: 1 -- C2 ran 41.6 ms with 1
-    // pixel per item, 43.7 with 4, r03zg), or the vpt_gpu_set_pixel_chunk value.  Every pixel keeps its own
-    // stream: samples do not depend on it.
-    uint64_t K = 1;
-    if (ctx->pixel_chunk > 0) {
-      K = (uint64_t)ctx->pixel_chunk;
-    } else {
-      const uint64_t lanes = (uint64_t)ctx->grid_blocks * vpt::kBlockThreads;
-      while (area % (2 * K) == 0 && items / (2 * K) >= 32 * lanes) K *= 2;
-    }
-    env.pixel_chunk = (uint32_t)K;
-    env.jid_count = items / K;
-  }
+  env.jid_count = plan.items;
+  env.pixel_chunk = plan.pixel_chunk;
   env.film = film ? film : ctx->film;
   env.records = records;
   env.tile_area = ctx->scene.tw * ctx->scene.th;
   env.prof_buf = ctx->prof;
-  env.order = nullptr;
-  env.perm = nullptr;
-  env.order_tail_k0 = 0;
-  env.order_tail_n = 0;
-  env.order_group = vpt::kOrderGroup;
-  // Partly filled launches (a few work items per resident lane: small frames, few waves, a GPU's share
-  // of a frame dealt over several): a launch lasts as long as its slowest jobs, and a job's lane runs
-  // faster with fewer waves per SIMD, so the grid is sized to round(1 + 1.8 x) blocks per CU (at most
-  // the resident capacity), x = items per resident lane.  Same jobs, same samples.  Measured (r03h,
-  // profiles/archive/r03h_grid_sweep.txt; C3 frames of spp waves, 4 / 5 / 6 / 7 blocks per CU, ms): spp 16
-  // (x 1.1) 54.5 / 55.0 / 55.4 / 57.5 (3: 51.5); spp 24 (x 1.7) 57.3 / 61.0 / 64.7 / 65.7; spp 32
-  // (x 2.3, the 8-GPU share) 70.4 / 66.9 / 67.5 / 71.2; spp 48 (x 3.4) 92.2 / 90.8 / 89.7 / 87.9; from
-  // spp 96 on (and C5's shares) the full grid is best.  C2 (262 144 jobs, x 0.57 -> 2 blocks per CU,
-  // r02g: 1 / 1.5 / 1.75 / 2 / 2.5 / 3 / 4 / 5 blocks per CU 167.7 / 124.4 / 112.9 / 98.7-99.3 / 104.4 /
-  // 104.5-105.3 / 106.7 / 109.9 ms).  (r02's rule, ~2 items per lane, gave 7 blocks from x 1.9 on.)
-  uint32_t blocks = (uint32_t)ctx->grid_blocks;
-  // Latency-bound launch (at most kSpreadLanes items per wavefront of the grid, e.g. C1's 4 096 jobs):
-  // the launch lasts as long as its slowest job, and a job runs fastest on a wavefront with few other
-  // paths (the wavefront executes every block any of its lanes needs).  Such a launch keeps the whole
-  // grid, the first ~items / wavefronts lanes of each wavefront take the jobs, and it runs with the
-  // latency gates (every block runs for one lane).  Measured, C1 (r02): 43.3 ms (256 blocks x 64
-  // lanes) -> 20.5 ms (1 792 blocks, one lane per wavefront, gates 1:65:1:1).  Same jobs, same samples.
-  const bool latency = env.jid_count <= kSpreadLanes * ((uint64_t)blocks * (vpt::kBlockThreads / 64));
-  const uint64_t cus = (uint64_t)ctx->cus;
-  if (!ctx->grid_user && !latency) {
-    const uint64_t resident_per_cu = std::max<uint64_t>(1, blocks / cus);
-    const double x = (double)env.jid_count / ((double)blocks * vpt::kBlockThreads);  // items per resident lane
-    const uint64_t per_cu = std::min<uint64_t>(resident_per_cu, (uint64_t)std::max(1.0, std::floor(1.5 + 1.8 * x)));
-    blocks = (uint32_t)std::min<uint64_t>(blocks, cus * per_cu);
-  }
-#ifdef VPT_JOB_LOG
-  const bool temp = ctx->scene.has_temperature != 0, dbg = events != nullptr;  // records = the job log
-#else
-  const bool temp = ctx->scene.has_temperature != 0, dbg = records != nullptr || events != nullptr;
-#endif
-  // The latency kernel (lane cold state in VGPRs, VPT_WAVES_LAT waves per SIMD) for launches that fill at
-  // most its resident grid anyway: latency-bound ones on its whole grid with the latency gates (C1 20.7-21.2
-  // -> 19.2-19.7 ms, r04e / r04z), and partly filled ones whose rule above gives <= lat_per_cu blocks per CU
-  // with the context's gates (C2 100.0-101.3 -> 95.7-96.6 ms, the 8-GPU C3 share of 32 waves 66.1-66.6 ->
-  // 65.1-65.3; with the latency gates they ran slower, 108.3-109.8 / 75.2-76.1 ms: its one-lane blocks add
-  // wave instructions to launches that are issue-bound; r04k, profiles/archive/r04k_lat_gated_ab.txt).  lat_mode 1
-  // forces it.  Same jobs, same samples.
-  const uint64_t lat_blocks = cus * (uint64_t)ctx->lat_per_cu;
-  // (a launch with light groups or a shutter always takes the throughput kernel: samples do not depend on the kernel)
-  const bool use_lat = !dbg && !feed && !groups && !shutter && ctx->lat_mode != 0 &&
-                       (ctx->lat_mode == 1 || (!ctx->grid_user && (latency || blocks <= lat_blocks)));
-  if (use_lat) blocks = (uint32_t)std::min<uint64_t>(latency ? lat_blocks : blocks, lat_blocks);
-  // Live-path compaction (vpt_gpu_set_compaction): partly filled launches of the latency kernel whose grid fits
-  // the compacting kernel's occupancy (its LDS exchange: 2 blocks per CU; C2 runs 2).
-  const bool compact = use_lat && !latency && ctx->compact_every > 0 &&
-                       (uint64_t)blocks <= cus * (uint64_t)std::max(0, ctx->compact_per_cu);
-  const uint64_t T = ctx->scene.T;
-  if (band) {
-    // the same-tile order restricted to the band (band_job), whatever the context's job order: the sample layout
-    // is built on it
-    if ((rc = ensure_order(ctx))) return rc;
-  } else if (!feed && ctx->order_mode != VPT_ORDER_JID && jid_begin % T == 0 && jid_count % T == 0 && jid_count < (1ULL << 32)) {
-    // whole waves: take the jobs in cost order (same jobs, same samples)
-    if ((rc = ensure_order(ctx))) return rc;
-    const uint32_t n = (uint32_t)(jid_count / T);
-    uint32_t tail = 0;  // VPT_ORDER_COST_WAVE_MAJOR
-    // Same-tile order only where each sample has a slot of its own (the ordered film): with film atomics a
-    // wavefront's 64 lanes would add to one pixel at once.  And not in partly filled launches (a few jobs per
-    // lane, the latency kernel with the context's gates), which last as long as their costliest jobs: r06ze, C2
-    // 98.1-98.5 vs 96.4-96.9 ms, C3's 8-GPU share (32 waves) 65.0-65.7 vs 62.6-63.6 with the cost tail.  Full
-    // launches: C3 321.8-322.0 vs 334.3-334.5 ms, C4 71.0-71.2 vs 80.2-80.7 (profiles/r06ze_same_tile_ab.txt).
-    const bool same_tile = ctx->order_mode == VPT_ORDER_COST_SAME_TILE && ordered && !ctx->frame_waves &&
-                           !(use_lat && !latency);
-    if (ctx->order_mode == VPT_ORDER_COST_TILE_MAJOR || same_tile) tail = n;
-    if (same_tile) env.order_group = 1;
-    if (ctx->order_mode == VPT_ORDER_COST_TAIL || (ctx->order_mode == VPT_ORDER_COST_SAME_TILE && !same_tile)) {
-      // the last ~6 x (resident lanes / T) waves (C3: 61 of 256): measured best of 2x..16x
-      const uint64_t lanes = (uint64_t)blocks * vpt::kBlockThreads;
-      const uint64_t want = ctx->order_tail_waves > 0 ? (uint64_t)ctx->order_tail_waves : (6 * lanes + T - 1) / T;
-      tail = (uint32_t)std::min<uint64_t>(n, want);
-    }
-    env.order = ctx->order;
-    env.order_tail_n = tail;
-    env.order_tail_k0 = (n - tail) * (uint32_t)T;
-  }
-  if (!feed && !band && ctx->perm && ctx->perm_n == jid_count && !ctx->scene.pixel_mode) env.perm = ctx->perm;
+  if ((band || plan.cost_order) && (rc = ensure_order(ctx))) return rc;  // (a band's sample layout is built on the ranks)
+  env.order = plan.cost_order ? ctx->order : nullptr;
+  env.order_tail_k0 = plan.order_tail_k0;
+  env.order_tail_n = plan.order_tail_n;
+  env.order_group = plan.order_group;
+  env.perm = !feed && !band && ctx->perm && ctx->perm_n == jid_count && !ctx->scene.pixel_mode ? ctx->perm : nullptr;
   float* samples = nullptr;
   // (while the drop-in's ordered frame is open its feeds own the sample buffer: other launches add with atomics)
   if (band) {
@@ -631,18 +693,10 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
     if (!samples)
       return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_tiles: the sample buffer would have to grow (" +
                                              std::to_string(bytes >> 20) + " MiB) while a feed of the context is open");
-  } else if (ordered && !ctx->frame_waves && (rc = ensure_samples(ctx, jid_count * per_job, samples))) {
+  } else if (plan.ordered && !ctx->frame_waves && (rc = ensure_samples(ctx, jid_count * per_job, samples))) {
     return rc;
   }
-  if (ctx->m2 && !feed && !samples)
-    return vpt::set_error(VPT_E_STATE, "render: a moment plane is attached and the sample buffer would have to grow while "
-                                       "a feed of the context is open (the launch would add with film atomics)");
-  if (groups && !samples)
-    return vpt::set_error(VPT_E_STATE, "render: light groups are attached and the sample buffer would have to grow while "
-                                       "a feed of the context is open (the launch would add with film atomics)");
-  if (shutter && !samples)
-    return vpt::set_error(VPT_E_STATE, "render: a shutter is attached and the sample buffer would have to grow while a "
-                                       "feed of the context is open (the launch would add with film atomics)");
+  if (!samples && attached.first()) return attached.refuse_grow();
   env.shutter = ctx->shutter_dev;
   env.shutter_n = (uint32_t)ctx->shutter.size();
   env.samples = samples;
@@ -654,43 +708,7 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   } else if (!feed) {
     ++ctx->atomic_launches;
   }
-  if (band) {
-    // The band's tile ranks: the whole frame's are the job order itself; another band's are filtered from it on
-    // the launch's stream -- after the wait above, so after the previous band launch has read the buffer -- unless
-    // the buffer still holds this band's.
-    env.band_rank = ctx->order;
-    env.band_slot_map = nullptr;
-    if (band->list) {
-      // a tile list (uploaded by vpt_gpu_render_tile_list): its ranks are filtered by the slot map, once per list
-      if (!ctx->band_rank || !ctx->list_dev || !ctx->list_slot_dev)
-        return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tile_list: no tile-list buffers (their allocation failed)");
-      if (!ctx->list_ranked) {
-        hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, 0u, band->tiles,
-                           ctx->band_rank, ctx->list_slot_dev);
-        VPT_HIP(hipGetLastError());
-        ctx->band_rank_lo = ctx->band_rank_hi = 0;  // (no longer a band's)
-        ctx->list_ranked = true;
-      }
-      env.band_rank = ctx->band_rank;
-      env.band_slot_map = ctx->list_slot_dev;
-    } else if (band->tile_lo != 0 || band->tiles != T) {
-      if (!ctx->band_rank) return vpt::set_error(VPT_E_NOMEM, "vpt_gpu_render_tiles: no tile-rank buffer (its allocation failed)");
-      if (ctx->band_rank_lo != band->tile_lo || ctx->band_rank_hi != band->tile_lo + band->tiles) {
-        hipLaunchKernelGGL(vpt::vpt_band_rank_kernel, dim3(1), dim3(256), 0, s, ctx->order, (uint32_t)T, band->tile_lo,
-                           band->tile_lo + band->tiles, ctx->band_rank, (const uint32_t*)nullptr);
-        VPT_HIP(hipGetLastError());
-        ctx->band_rank_lo = band->tile_lo;
-        ctx->band_rank_hi = band->tile_lo + band->tiles;
-        ctx->list_ranked = false;
-      }
-      env.band_rank = ctx->band_rank;
-    }
-    env.band_waves = band->waves;
-    env.band_T = (uint32_t)T;
-    env.band_tile_lo = band->tile_lo;
-    env.band_groups = vpt::band_groups(band->waves, band->group);
-    env.band_group = band->group;
-  }
+  if (band && (rc = band_ranks(ctx, *band, s, env))) return rc;
   uint32_t slot = 0;
   if ((rc = take_slot(ctx, s, slot))) return rc;
   env.job_counter = ctx->job_counter + 2 * slot;
@@ -708,131 +726,20 @@ int vpt::host::render(vpt_gpu_ctx* ctx, uint64_t jid_begin, uint64_t jid_count, 
   env.frame_slots = env.frame ? ctx->frame_waves * ctx->frame_tiles : 0;
   env.frame_tile_lo = ctx->frame_tile_lo;
   env.frame_tiles = ctx->frame_tiles;
-  env.compact_every = 0;
+  env.compact_every = plan.compact_every;
   env.event_count = ctx->job_counter + 2 * slot + 1;
   env.event_cap = event_cap;
   if (slot_out) *slot_out = slot;
-  // (a compacting launch reads the context's scene, whose wave_lanes is 64: a path moved into another thread's
-  // slot must be able to fetch there -- with fewer fetching lanes per wavefront, live paths packed into the
-  // first slots would leave the fetching slots to finished ones)
-  const vpt::DevScene* scene =
-      latency || (use_lat && ctx->lat_ungated && !compact) ? ctx->scene_lat_dev : ctx->scene_dev;
-  if (shutter) {  // the Shutter instantiations of the throughput kernels, plain or band, with or without Groups
-    using vpt::vpt_integrate_kernel;
-    auto pick = [&](auto plain, auto runs, auto with_temp) { return temp ? with_temp : ctx->use_runs ? runs : plain; };
-    auto kernel = groups ? (band ? pick(vpt_integrate_kernel<false, false, false, false, false, false, true, false, true, true>,
-                                        vpt_integrate_kernel<false, false, true, false, false, false, true, false, true, true>,
-                                        vpt_integrate_kernel<true, false, false, false, false, false, true, false, true, true>)
-                                 : pick(vpt_integrate_kernel<false, false, false, false, false, false, false, false, true, true>,
-                                        vpt_integrate_kernel<false, false, true, false, false, false, false, false, true, true>,
-                                        vpt_integrate_kernel<true, false, false, false, false, false, false, false, true, true>))
-                         : (band ? pick(vpt_integrate_kernel<false, false, false, false, false, false, true, false, false, true>,
-                                        vpt_integrate_kernel<false, false, true, false, false, false, true, false, false, true>,
-                                        vpt_integrate_kernel<true, false, false, false, false, false, true, false, false, true>)
-                                 : pick(vpt_integrate_kernel<false, false, false, false, false, false, false, false, false, true>,
-                                        vpt_integrate_kernel<false, false, true, false, false, false, false, false, false, true>,
-                                        vpt_integrate_kernel<true, false, false, false, false, false, false, false, false, true>));
-    if (scene == ctx->scene_dev) scene = ctx->scene_full_dev;  // (the full-launch gates, as below)
-    // (light groups without a temperature grid: region 1 is the host's, as below)
-    if (groups && !temp) VPT_HIP(hipMemsetAsync(samples + env.group_stride, 0, env.group_stride * sizeof(float), s));
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-  } else if (groups) {  // the Groups instantiations of the throughput kernels, plain or band (never a debug launch)
-    auto kernel = band ? (temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, true, false, true>
-                          : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, true, false, true>
-                                          : vpt::vpt_integrate_kernel<false, false, false, false, false, false, true, false, true>)
-                       : (temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, false, false, true>
-                          : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, false, false, true>
-                                          : vpt::vpt_integrate_kernel<false, false, false, false, false, false, false, false, true>);
-    if (scene == ctx->scene_dev) scene = ctx->scene_full_dev;  // (the full-launch gates, as below)
-    // no temperature grid: no emission.  The kernel leaves region 1 alone; the pass below adds its +0.0 samples.
-    if (!temp) VPT_HIP(hipMemsetAsync(samples + env.group_stride, 0, env.group_stride * sizeof(float), s));
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-  } else if (band) {  // the Band instantiations of the same kernels, by the same rules
-    if (use_lat) {
-      env.compact_every = (uint32_t)std::max(1, ctx->compact_every);
-      if (compact) {
-        auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true, true, false, true>
-                           : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true, true, false, true>
-                                           : vpt::vpt_integrate_kernel<false, false, false, true, true, false, true>;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), vpt::kXchgBytes, s, env, scene, ctx->counters);
-      } else {
-        auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true, false, false, true>
-                           : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true, false, false, true>
-                                           : vpt::vpt_integrate_kernel<false, false, false, true, false, false, true>;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-      }
-    } else {
-      auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, true>
-                         : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, true>
-                                         : vpt::vpt_integrate_kernel<false, false, false, false, false, false, true>;
-      if (scene == ctx->scene_dev) scene = ctx->scene_full_dev;  // (the full-launch gates, as below)
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-    }
-  } else if (use_lat) {
-    env.compact_every = (uint32_t)std::max(1, ctx->compact_every);
-    if (compact) {
-      auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true, true>
-                         : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true, true>
-                                         : vpt::vpt_integrate_kernel<false, false, false, true, true>;
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), vpt::kXchgBytes, s, env, scene, ctx->counters);
-    } else {
-      auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, true>
-                         : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, true>
-                                         : vpt::vpt_integrate_kernel<false, false, false, true>;
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-    }
-  } else if (feed) {  // (never a debug launch: no records or events)
-    auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, true>
-                       : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, true>
-                                       : vpt::vpt_integrate_kernel<false, false, false, false, false, true>;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-  } else {
-    auto kernel = temp ? (dbg ? vpt::vpt_integrate_kernel<true, true, false> : vpt::vpt_integrate_kernel<true, false, false>)
-                       : ctx->use_runs
-                           ? (dbg ? vpt::vpt_integrate_kernel<false, true, true> : vpt::vpt_integrate_kernel<false, false, true>)
-                           : (dbg ? vpt::vpt_integrate_kernel<false, true, false> : vpt::vpt_integrate_kernel<false, false, false>);
-    // (production launches of the throughput kernel read the full-launch gates, vpt_gpu_set_full_tuning; a
-    // latency-bound one on it keeps the latency copy: its wave_lanes)
-    if (!dbg && scene == ctx->scene_dev) scene = ctx->scene_full_dev;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, scene, ctx->counters);
-  }
-  ctx->last_gate_set = scene == ctx->scene_full_dev ? VPT_GATES_FULL
-                       : scene == ctx->scene_lat_dev ? VPT_GATES_LATENCY : VPT_GATES_CONTEXT;  // (vpt_gpu_gate_info)
-  // (the instantiation just launched splits the evaluation: a density-only production launch of a throughput kernel)
-  ctx->last_eval_split = vpt::kernel_eval_split(temp, dbg, use_lat) ? 1 : 0;
-  VPT_HIP(hipGetLastError());
-  const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
-  if (band) {  // the film's pixels of the band, in wave order (sample counts included)
-    const uint32_t chunks = (ctx->scene.tile_area + 63u) / 64u;
-    const uint32_t* const list = band->list ? ctx->list_dev : nullptr;
-    hipLaunchKernelGGL(ctx->m2 ? vpt::vpt_band_order_kernel<true> : vpt::vpt_band_order_kernel<false>,
-                       dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev, env.film, (const float*)samples,
-                       band->tile_lo, band->waves, env.band_groups, band->group, list, ctx->m2);
-    VPT_HIP(hipGetLastError());
-    // the group planes: the same pass over each group's region (w += 1, xyz += imaging_ratio * Lg, in wave order)
-    for (uint64_t g = 0; groups && g < 3; ++g) {
-      hipLaunchKernelGGL(vpt::vpt_band_order_kernel<false>, dim3(band->tiles * chunks), dim3(64), 0, s, ctx->scene_dev,
-                         ctx->groups + g * npix * 4, (const float*)samples + (g + 1) * env.group_stride, band->tile_lo,
-                         band->waves, env.band_groups, band->group, list, (float*)nullptr);
-      VPT_HIP(hipGetLastError());
-    }
-    VPT_HIP(hipEventRecord(ctx->samples_done, s));
-    ctx->samples_used = true;
-  } else if (samples) {  // the film, pixel by pixel in wave order (sample counts included)
-    const uint64_t threads = ctx->scene.T * (uint64_t)ctx->scene.tile_area;
-    hipLaunchKernelGGL(ctx->m2 ? vpt::vpt_film_order_kernel<true> : vpt::vpt_film_order_kernel<false>,
-                       dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ctx->scene_dev, env.film,
-                       (const float*)samples, jid_begin, jid_count, ctx->m2);
-    VPT_HIP(hipGetLastError());
-    for (uint64_t g = 0; groups && g < 3; ++g) {  // the group planes, as above
-      hipLaunchKernelGGL(vpt::vpt_film_order_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
-                         ctx->scene_dev, ctx->groups + g * npix * 4, (const float*)samples + (g + 1) * env.group_stride,
-                         jid_begin, jid_count, (float*)nullptr);
-      VPT_HIP(hipGetLastError());
-    }
-    VPT_HIP(hipEventRecord(ctx->samples_done, s));
-    ctx->samples_used = true;
+  // 5. the launch and the film passes
+  if (plan.zero_region1) VPT_HIP(hipMemsetAsync(samples + env.group_stride, 0, env.group_stride * sizeof(float), s));
+  const vpt::DevScene* const scene = plan.gate_set == VPT_GATES_FULL      ? ctx->scene_full_dev
+                                     : plan.gate_set == VPT_GATES_LATENCY ? ctx->scene_lat_dev
+                                                                          : ctx->scene_dev;
+  if ((rc = launch_integrate(ctx, plan.variant, plan.blocks, plan.lds_bytes, s, env, scene))) return rc;
+  if (samples) {
+    if ((rc = film_passes(ctx, env, band, groups, jid_begin, jid_count, s))) return rc;
   } else if (!feed) {  // a feed adds its sample counts when it is closed (vpt_tile_count_kernel)
+    const uint64_t npix = (uint64_t)ctx->scene.W * (uint64_t)ctx->scene.H;
     hipLaunchKernelGGL(vpt::vpt_count_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, ctx->scene_dev,
                        env.film, jid_begin, jid_count);
     VPT_HIP(hipGetLastError());
@@ -939,26 +846,18 @@ int size_grid(vpt_gpu_ctx* ctx, bool runs) {
   const bool has_temperature = ctx->has_temperature;
   int per_cu = 0, cus = 0;
   // sized for the production kernel of this scene; the debug variant is launched with the same grid
-  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false>
-                           : (runs ? vpt::vpt_integrate_kernel<false, false, true> : vpt::vpt_integrate_kernel<false, false, false>),
-      vpt::kBlockThreads, 0));
+  vpt::KernelVariant v = vpt::base_variant(has_temperature, runs);
+  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, integrate_kernel(v), vpt::kBlockThreads, 0));
   VPT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   if (per_cu < 1) per_cu = 1;
   if (!ctx->grid_user) ctx->grid_blocks = per_cu * cus;
   int lat_per_cu = 0;
-  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &lat_per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false, true>
-                               : (runs ? vpt::vpt_integrate_kernel<false, false, true, true>
-                                       : vpt::vpt_integrate_kernel<false, false, false, true>),
-      vpt::kBlockThreads, 0));
+  v.lat = true;
+  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&lat_per_cu, integrate_kernel(v), vpt::kBlockThreads, 0));
   ctx->lat_per_cu = std::max(1, std::min(lat_per_cu, per_cu));
   int compact_per_cu = 0;
-  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &compact_per_cu, has_temperature ? vpt::vpt_integrate_kernel<true, false, false, true, true>
-                                   : (runs ? vpt::vpt_integrate_kernel<false, false, true, true, true>
-                                           : vpt::vpt_integrate_kernel<false, false, false, true, true>),
-      vpt::kBlockThreads, vpt::kXchgBytes));
+  v.compact = true;
+  VPT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&compact_per_cu, integrate_kernel(v), vpt::kBlockThreads, vpt::kXchgBytes));
   ctx->compact_per_cu = compact_per_cu;
   ctx->cus = cus > 0 ? cus : 1;
   return VPT_OK;
@@ -1737,14 +1636,9 @@ int vpt_gpu_render_adaptive_fused(vpt_gpu_ctx* ctx, const vpt_adaptive_params* p
   if ((rc = take_slot(ctx, s, slot))) return rc;
   env.job_counter = ctx->job_counter + 2 * slot;
   env.event_count = ctx->job_counter + 2 * slot + 1;
-  const bool temp = ctx->scene.has_temperature != 0;
-  auto kernel = temp ? vpt::vpt_integrate_kernel<true, false, false, false, false, false, false, true>
-                     : ctx->use_runs ? vpt::vpt_integrate_kernel<false, false, true, false, false, false, false, true>
-                                     : vpt::vpt_integrate_kernel<false, false, false, false, false, false, false, true>;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(vpt::kBlockThreads), 0, s, env, ctx->scene_full_dev, ctx->counters);
-  ctx->last_gate_set = VPT_GATES_FULL;
-  ctx->last_eval_split = vpt::kernel_eval_split(temp, false, false) ? 1 : 0;
-  VPT_HIP(hipGetLastError());
+  vpt::KernelVariant gang = vpt::base_variant(ctx->scene.has_temperature != 0, ctx->use_runs);
+  gang.gang = true;
+  if ((rc = launch_integrate(ctx, gang, blocks, 0, s, env, ctx->scene_full_dev))) return rc;
   ++ctx->ordered_launches;
   VPT_HIP(hipMemcpyAsync(waves_T_host, ctx->gang_waves, (size_t)T * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   VPT_HIP(hipMemcpyAsync(err_T_host, ctx->tile_err, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, s));

@@ -10,31 +10,11 @@
 #include "vpt_depth.h"
 #include "vpt_internal.h"
 #include "vpt_launch.h"
+#include "vpt_variant.h"
 
 namespace vpt {
 
 constexpr int kCounterCount = CNT_COUNT;
-// Minimum waves per SIMD (launch bounds): 7 for the production density-only kernel (72 VGPRs; the
-// cold lane state lives in LDS, see LaneCold), 6 for the temperature kernel (C4: 3748 Msps at its
-// natural 5, 3809 at 6, 3684 at 7), 4 for the per-sample-record / event variants.  The kernel is latency-bound enough that occupancy pays: persistent grids of 3/4/5
-// blocks per CU measured 802/956/1067 Msps on C3 with one binary; 6 waves 1155, 7 waves 1194.
-#ifndef VPT_WAVES_FAST
-#define VPT_WAVES_FAST 7
-#endif
-#ifndef VPT_WAVES_SLOW
-#define VPT_WAVES_SLOW 4
-#endif
-#ifndef VPT_WAVES_TEMP
-#define VPT_WAVES_TEMP 6
-#endif
-// The latency kernel (partly filled and latency-bound launches: C1, C2, a GPU's small share of a frame):
-// at most VPT_WAVES_LAT waves per SIMD run anyway there, so it trades occupancy for registers -- the
-// lane's cold state in VGPRs instead of LDS (no LDS round trips on the per-pixel / per-bounce chain)
-// and a 512 / VPT_WAVES_LAT register budget.
-#ifndef VPT_WAVES_LAT
-#define VPT_WAVES_LAT 4
-#endif
-
 // The lanes' cold state (vpt_integrator.h LaneCold), one slot per thread of the integrator's block.
 __shared__ LaneCold g_lane_cold[kBlockThreads];
 // LDS copies of the small lookup tables the evaluation reads per lane (logf's 16 x 2 doubles; the
@@ -157,7 +137,7 @@ constexpr uint32_t kGangMaxArea = 256;
 // Gang: a gang launch's (vpt_gpu_render_adaptive_fused): the wavefront's fetch is gang_next, film_add stores into the
 // wavefront's scratch; every other launch compiles them out.
 // Split: the density evaluation runs as two halves of one lane_iteration (kEvalSplit, vpt_integrator.h eval_issue);
-// the kernel sets it by kernel_eval_split.
+// the kernel sets it by variant_eval_split (vpt_variant.h).
 // Groups: light groups (vpt_gpu_set_light_groups; 1: sun and sky, 2: emission too -- a temperature grid): the
 // accumulators of env_groups (vpt_integrator.h) in LDS and three more stores per sample in film_add; every other
 // launch compiles them out.
@@ -167,7 +147,6 @@ constexpr uint32_t kGangMaxArea = 256;
 template <bool RegCold, bool Feed = false, bool Band = false, bool Gang = false, bool Split = false, int Groups = 0,
           bool Shutter = false>
 struct KernelEnvT {
-  static_assert(!(Shutter && (RegCold || Feed || Gang)), "a shutter runs the throughput kernels, plain or band");
   static constexpr bool kShutter = Shutter;  // (lane_iteration's fetch and pixel blocks)
   __device__ __forceinline__ void shutter_begin(uint32_t entry) { g_shutter_at[threadIdx.x] = entry * 16u; }
   // Row r of the lane's entry (16 bytes, one load per lane: a wavefront's lanes hold up to 64 different entries).
@@ -175,7 +154,6 @@ struct KernelEnvT {
   __device__ __forceinline__ float4 shutter_row(int r) const {
     return reinterpret_cast<const float4*>(args()->shutter + g_shutter_at[threadIdx.x])[r];
   }
-  static_assert(!(Groups && (RegCold || Feed || Gang)), "light groups run the throughput kernels, plain or band");
   static constexpr bool kGroups = Groups != 0;  // (primary_event, nee_done and the pixel block)
   __device__ __forceinline__ void group_begin() {
     for (int c = 0; c < 3; ++c) {
@@ -221,9 +199,6 @@ struct KernelEnvT {
     k[2] = sky ? S.le_inf[2] : 0.0f;
   }
   static_assert(!(RegCold && Split), "the latency kernels evaluate whole");
-  static_assert(!(RegCold && Feed), "feeds run the throughput kernels only");
-  static_assert(!(Band && Feed), "band launches are no feeds");
-  static_assert(!(Gang && (RegCold || Feed || Band)), "gang launches run the plain throughput kernels only");
   static constexpr bool kGang = Gang;  // (lane_iteration's fetch block)
   static constexpr bool kEvalSplit = Split;  // (lane_iteration's evaluation)
   __device__ __forceinline__ ArgsPtr args() const {
@@ -740,7 +715,6 @@ struct KernelEnvT {
 // A path's operations and draws never depend on the thread that runs it (its RNG state and every value it reads
 // travel with it; the gates only choose when a block runs), so samples are bit-identical; only the order of the
 // film's fp32 atomics changes.  The HDDA step counter stays with the thread (it is summed per launch).
-constexpr int kXWords = 60;  // 54 state words (58 with a temperature grid), padded to uint4
 __device__ __forceinline__ uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
 __device__ __forceinline__ float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
 template <bool HasTemp>
@@ -799,8 +773,6 @@ __device__ __forceinline__ void xchg_unpack(Lane& ln, LaneCold& lc, const uint32
 #endif
   (void)n;
 }
-// Dynamic LDS of the compacting kernel: [kXWords / 4][kBlockThreads] uint4 (61 440 B).
-constexpr size_t kXchgBytes = (size_t)kXWords * kBlockThreads * sizeof(uint32_t);
 
 template <bool HasTemp, bool Runs, class Env>
 __device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc, Env& env) {
@@ -861,17 +833,13 @@ __device__ __forceinline__ void compact_loop(ScenePtr sp, Lane& ln, LaneCold& lc
   }
 }
 
-// The instantiations that split the density evaluation: the density-only production kernels of the throughput
-// family -- plain, run-skipping, feed, band and gang.  The stencil's eight registers fit across the rare blocks of
-// the 72-VGPR kernel only: the temperature kernel (80 VGPRs at 6 waves, none to spare), the records / events kernels
-// and the latency and compacting kernels (the lane's cold state in VGPRs) evaluate whole, with the code they had.
-constexpr bool kernel_eval_split(bool has_temp, bool debug, bool lat) { return !has_temp && !debug && !lat; }
-
 // counters[] order = vpt_counters field order
 template <bool HasTemp, bool Debug, bool Runs, bool Lat = false, bool Compact = false, bool Feed = false, bool Band = false,
           bool Gang = false, bool Groups = false, bool Shutter = false>
-__global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT : (Debug ? VPT_WAVES_SLOW : (HasTemp ? VPT_WAVES_TEMP : VPT_WAVES_FAST)))) void vpt_integrate_kernel(KernelArgs args, const DevScene* scene,
-                                                                       unsigned long long* counters) {
+__global__ __launch_bounds__(kBlockThreads, variant_waves_per_simd(KernelVariant{HasTemp, Debug, Runs, Lat, Compact, Feed, Band, Gang, Groups, Shutter}))
+void vpt_integrate_kernel(KernelArgs args, const DevScene* scene, unsigned long long* counters) {
+  constexpr KernelVariant kVariant{HasTemp, Debug, Runs, Lat, Compact, Feed, Band, Gang, Groups, Shutter};
+  static_assert(variant_valid(kVariant), "no such instantiation: vpt_variant.h variant_valid is the rule");
   (void)args;  // read through KernelEnvT::args()
   if (threadIdx.x < kCounterCount) g_wg_counters[threadIdx.x] = 0;
   if (threadIdx.x < 32) g_logf_tab[threadIdx.x >> 1][threadIdx.x & 1] = math::kLogfTab[threadIdx.x >> 1][threadIdx.x & 1];
@@ -885,10 +853,6 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
   __syncthreads();
   if (threadIdx.x % 64 == 0) g_wg_prof[PT_COUNT + threadIdx.x / 64] = clock64();
 #endif
-  static_assert(!(Band && Debug), "band launches have no records or events");
-  static_assert(!(Gang && (Debug || Lat || Compact || Feed || Band)), "gang launches run the plain throughput kernels only");
-  static_assert(!(Groups && (Debug || Lat || Compact || Feed || Gang)), "light groups run the throughput kernels, plain or band");
-  static_assert(!(Shutter && (Debug || Lat || Compact || Feed || Gang)), "a shutter runs the throughput kernels, plain or band");
   if constexpr (Gang) {
     if (threadIdx.x < kBlockThreads / 64) {  // no tile, no group (read by the wavefront itself: no barrier needed)
       g_gang[threadIdx.x][0] = 0xffffffffu;
@@ -896,7 +860,7 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
     }
     __syncthreads();
   }
-  KernelEnvT<Lat, Feed, Band, Gang, kernel_eval_split(HasTemp, Debug, Lat), Groups ? (HasTemp ? 2 : 1) : 0, Shutter> env;
+  KernelEnvT<Lat, Feed, Band, Gang, variant_eval_split(kVariant), Groups ? (HasTemp ? 2 : 1) : 0, Shutter> env;
   env.reg_cold = nullptr;
   Lane ln;
   lane_init(ln);
@@ -905,7 +869,6 @@ __global__ __launch_bounds__(kBlockThreads, Compact ? 2 : (Lat ? VPT_WAVES_LAT :
   cold_init(env.cold());
   const ScenePtr sp = (ScenePtr)scene;
   if constexpr (Compact) {
-    static_assert(Lat && !Debug, "compaction runs in the latency kernel only");
     compact_loop<HasTemp, Runs>(sp, ln, lc_reg, env);
   } else
   while (ln.state != ST_DONE) {
