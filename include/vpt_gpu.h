@@ -631,7 +631,7 @@ int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, fl
  * not in (0, 1) (a NaN included), opacities not strictly ascending.  VPT_E_STATE while a feed of the context is
  * launched and not closed, and while a shutter is attached (the depth would be another camera's).  Out of scope:
  * depth under a shutter, the drop-in vpt_gpu::run and feeds, the multi-GPU modes, mean collision depth and deep
- * output, position and motion-vector planes. */
+ * output, position planes (motion vectors: the block "Temporal" below). */
 #define VPT_DEPTH_MAX_LEVELS 4
 int vpt_gpu_render_depth(vpt_gpu_ctx* ctx, uint32_t sub, uint32_t n_levels, const float* opacity_host,
                          float* depth_device /* [n_levels][H][W] */, float* reach_device /* same shape, may be NULL */,
@@ -680,7 +680,7 @@ int vpt_gpu_render_depth(vpt_gpu_ctx* ctx, uint32_t sub, uint32_t n_levels, cons
  * guide; sigma_l, rel_floor or a used guide_sigma that is not > 0 (NaN included); a film that is not 16-byte or a
  * plane that is not 4-byte aligned; an output that overlaps an input or the other output.  VPT_E_STATE while a feed of the context is launched and not closed (the tile-list launch's
  * rule: the call allocates and must not queue behind a launch that holds the device).  Out of scope: the drop-in
- * vpt_gpu::run and feeds (no moment plane there), the multi-GPU modes, temporal filtering, colour-channel
+ * vpt_gpu::run and feeds (no moment plane there), the multi-GPU modes (temporal: the block below), colour-channel
  * variances (only Y has a moment), learned denoisers. */
 typedef struct vpt_denoise_params {
   uint32_t iterations; /* 1..6; 4 is a good default */
@@ -692,6 +692,81 @@ typedef struct vpt_denoise_params {
 int vpt_gpu_denoise(vpt_gpu_ctx* ctx, const vpt_denoise_params* p, const float* film_device, const float* m2_device,
                     const float* const* guides_device /* n_guides device planes float[H][W]; may be NULL when 0 */,
                     float* out_film_device, float* var_out_device /* may be NULL */, void* hip_stream);
+
+/* Temporal.  Accumulation across the frames of a sequence: the previous frame's accumulated film, reprojected through
+ * the current frame's depth planes, is added to the current film.  A film is sums and a count, so history is added,
+ * not blended; the result is an ordinary film with a matching moment plane, which vpt_gpu_denoise and every film
+ * consumer take unchanged, and -- with this frame's depth planes and camera -- it is the next frame's history (the
+ * caller swaps two buffer sets).  Asynchronous on `hip_stream`; takes a launch slot, so vpt_gpu_sync covers it; reads
+ * its inputs only and allocates nothing.  The current camera is the context's scene camera (vpt_gpu_set_scene);
+ * `prev_cam`, the camera the history was rendered with, becomes camera floats by the code that derives the scene's
+ * camera and a shutter entry (vpt_shutter_entry), under vpt_gpu_set_shutter's validation.
+ *
+ * Arithmetic (fp32, not contracted, only + - * /, sqrtf, floorf, fabsf, comparisons and selects, divisions and square
+ * roots correctly rounded, in exactly this order: csrc/vpt_temporal.h is the code, tests/temporal_ref.py its numpy
+ * restatement, and the device, the host build and numpy give the same bytes).  dot(u, v) = u0 v0 + (u1 v1 + u2 v2);
+ * cross(u, v) = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0).  L, t, pos: cam_L (row-major), cam_t and the position
+ * of the current camera; L', t', pos': the previous camera's; L0', L1': the first two columns of L'.
+ *   Previous camera, once, on the host (passed as kernel arguments):
+ *     n = cross(L0', L1');  nn = dot(n, n);  a = cross(L1', n) / nn;  b = cross(n, L0') / nn   (per component);
+ *     tn = dot(t', n);  ta = dot(t', a);  tb = dot(t', b).
+ *   These solve t' + L0' rx + L1' ry = lambda q for a direction q:  lambda = tn / dot(q, n),
+ *   rx = lambda dot(q, a) - ta,  ry = lambda dot(q, b) - tb.
+ *   Per pixel p = (x, y):
+ *   Depth.  z = depth[k][p] for the largest k < n_levels with depth[k][p] > 0 (the reached levels are a prefix);
+ *     foreground iff there is one, else background.  The history's taps use the same rule on hist_depth.
+ *   Position.  rx = (float)x + 0.5f, ry = (float)y + 0.5f;  dv_i = t_i + (L_i0 rx + (L_i1 ry + L_i2 0.0f));
+ *     n2 = dv0 dv0 + (dv1 dv1 + dv2 dv2);  d = dv / sqrtf(n2) when n2 > 0  (Camera::generate_ray without jitter, the
+ *     integrator's expressions: the direction the depth is measured along).
+ *     Foreground: q = (pos + z d) - pos',  r = sqrtf(dot(q, q)).  Background: q = d (a point at infinity: rotation only).
+ *   Projection.  lambda, px = rx', py = ry' as above.  There is a projection iff lambda > 0 and lambda, px and py are
+ *     finite.  motion_out[p] = (px - rx, py - ry), else a NaN pair; written whether or not a history is given.
+ *   Taps.  fx = px - 0.5f, fy = py - 0.5f, in range iff -1 < fx < W and -1 < fy < H (tested before any conversion to
+ *     an integer);  x0 = floorf(fx), ax = fx - x0, likewise y.  The taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *     (x0 + 1, y0 + 1), in this order, have w = (1 - ax)(1 - ay), ax (1 - ay), (1 - ax) ay, ax ay.  A tap q is usable
+ *     iff it lies in the image, its count n_q = hist_film[q].w >= 1 (NaN is not) and it agrees in depth -- foreground:
+ *     z_q > 0 and fabsf(z_q - r) <= depth_tol r; background: z_q is background.  The exclusion is a select, so NaN
+ *     or garbage in an unusable tap cannot leak.  Sequentially over the usable taps:
+ *       ws += w;   s += w (xyz_q / n_q);   sm += w (m2_q / n_q);   sn += w n_q.
+ *   History is used iff a history is given, n_c = film[p].w >= 1, there is a projection in range and ws >= 0.25f
+ *     (VPT_TEMPORAL_MIN_WEIGHT: one far corner tap is not blown up by the renormalisation).  Then
+ *       c_h = s / ws;   s_h = sm / ws;   n_0 = sn / ws;   c_c = xyz / n_c;
+ *       v_c = n_c >= 2 ? max(m2 / n_c - c_c.y c_c.y, 0) / (n_c - 1) : c_c.y c_c.y      (the denoiser's prepare)
+ *       v_h = max(s_h - c_h.y c_h.y, 0) / max(n_0 - 1, 1);
+ *       e   = fabsf(c_c.y - c_h.y) / ((sigma_r sqrtf(v_c + v_h) + rel_floor c_c.y) + 1e-20f);
+ *       n_h = min(n_0, max_history) / (1 + e e)                  (a rational rejection, as the denoiser's falloff)
+ *     and, iff n_h > 0 (a NaN or a fully rejected history adds nothing):
+ *       out.xyz = xyz + n_h c_h;   out.w = n_c + n_h;   out_m2 = m2 + n_h s_h;   hist_n_out = n_h.
+ *   Every other pixel -- no current samples, no usable history, every pixel when the history pointers are NULL --
+ *   passes through: out_film and out_m2 are the inputs' bytes, copied, and hist_n_out is +0.
+ *
+ * Kernel: vpt_temporal_kernel, blocks of 64 x 4 pixels, one lane per pixel, so a tap is one 16-byte film load plus
+ * the plane's and the depth planes' dwords; no LDS, no atomics, no scratch, fixed trip counts; the level is picked
+ * with selects.  Alignment: the three films 16 bytes, every plane 4 bytes.
+ *
+ * VPT_E_INVALID: a null context, params, film, plane, depth, previous camera, output film or output plane; a history
+ * of which only some pointers are given; n_levels outside 1..4; max_history, depth_tol, sigma_r or rel_floor not > 0
+ * (NaN included); a misaligned film or plane; a previous camera vpt_gpu_set_shutter would refuse; an output that
+ * overlaps an input or another output.  The arguments are checked before the context is.  Out of scope: motion of
+ * the medium (volume sequences), light groups, shutter frames, the drop-in vpt_gpu::run and feeds, the multi-GPU
+ * modes, neighbourhood colour clamping, history length as a filter parameter of the a-trous pass, accumulated
+ * variance as the adaptive stopping rule. */
+#define VPT_TEMPORAL_MIN_WEIGHT 0.25f
+typedef struct vpt_temporal_params {
+  uint32_t n_levels; /* 1..VPT_DEPTH_MAX_LEVELS depth planes per frame, as vpt_gpu_render_depth writes them */
+  float max_history; /* > 0: cap of the history's sample count per pixel */
+  float depth_tol;   /* > 0: relative depth tolerance of a history tap; default 0.1 */
+  float sigma_r;     /* > 0: Y rejection scale in standard deviations; default 4 */
+  float rel_floor;   /* > 0: relative floor of that scale (the denoiser's meaning); default 1e-3 */
+} vpt_temporal_params;
+int vpt_gpu_temporal(vpt_gpu_ctx* ctx, const vpt_temporal_params* p, const float* film_device, const float* m2_device,
+                     const float* depth_device /* current frame: [H][W][4], [H][W], [n_levels][H][W] */,
+                     const vpt_shutter_camera* prev_cam /* the camera the history was rendered with */,
+                     const float* hist_film_device, const float* hist_m2_device,
+                     const float* hist_depth_device /* the same shapes; all three NULL: no history */,
+                     float* out_film_device, float* out_m2_device /* an ordinary film and moment plane */,
+                     float* motion_out_device /* [H][W][2], may be NULL */,
+                     float* hist_n_out_device /* [H][W], may be NULL */, void* hip_stream);
 
 /* The drop-in's ordered frame (vpt_run.hpp: vpt_gpu::run's film, bit-identical to the reference's).  A feed's jobs
  * arrive in the provider's order and its film is progressive, so its launch adds samples with fp32 atomics; with a

@@ -52,6 +52,18 @@ surface and the median free-flight depth) the distance from the camera at which 
 that opacity, 0 where it never does.  ``--depth-sub N`` sets the sub-rays per axis (default 1), ``--depth-reach-out r.npy``
 saves the fraction of sub-rays that reached each level.  One deterministic pass after the frame, with every driver and in
 sequences; not with a shutter, and the other three flags need ``--depth-out``: exit 1 before a device is touched.
+``--temporal`` (sequences only) accumulates the frames: after frame k is rendered (one ordered launch
+with its moment plane, or either adaptive driver) and its depth planes are computed (the ``--depth-out`` call when that
+runs at the default levels and one sub-ray), Integrator.temporal reprojects frame k - 1's accumulated film through the
+depth planes and adds it; ``--denoise`` then filters the accumulated film and plane, and the PNG is written from the
+result.  Frame k renders with seed ``seed + k`` (mod 2^32): with one seed every frame reuses the same job streams, the
+noise of consecutive frames is correlated in screen space and accumulation gains nothing.  Frame 0 has no history: its
+files equal the run without ``--temporal``.  ``--temporal-history N`` caps the history's sample count per pixel (default
+4 x num_waves), ``--temporal-depth-tol T`` (default 0.1) and ``--temporal-sigma S`` (default 4) set the depth tolerance
+and the rejection scale; ``--motion-out mv_%03d.npy`` saves the motion plane (float32 [H][W][2], pixels; NaN where a
+point has no projection), ``--accumulated-film-out acc_%03d.npy`` the accumulated film; ``--film-out`` still saves the raw
+film, and ``--moments-out`` saves the plane the denoiser read: the accumulated one.  Not without ``--frames`` / ``--camera-path``, nor with a shutter, ``--volume-sequence``, ``--light-groups`` /
+``--relight`` or ``--rng-mode pixel``, and the other five flags need ``--temporal``: exit 1 before a device is touched.
 ``--rng-mode pixel`` renders the plain uniform frame in the pixel RNG mode (one stream per pixel sample; not the
 reference's samples).
 Exits 1 on a fatal error, like vptFATAL.
@@ -201,6 +213,16 @@ def main(argv=None) -> int:
     ap.add_argument("--depth-sub", type=int, default=None, metavar="N", help="depth: N x N sub-rays per pixel, 1..8 (default 1)")
     ap.add_argument("--depth-reach-out", default=None,
                     help="depth: save the fraction of sub-rays that reached each level (.npy, float32 [K][H][W])")
+    ap.add_argument("--temporal", action="store_true",
+                    help="sequence: add the previous frame's accumulated film, reprojected by depth (Integrator.temporal)")
+    ap.add_argument("--temporal-history", type=float, default=None, metavar="N",
+                    help="temporal: cap of the history's sample count per pixel (default 4 x num_waves)")
+    ap.add_argument("--temporal-depth-tol", type=float, default=None, metavar="T",
+                    help="temporal: relative depth tolerance of a history tap (default 0.1)")
+    ap.add_argument("--temporal-sigma", type=float, default=None, metavar="S",
+                    help="temporal: Y rejection scale in standard deviations (default 4)")
+    ap.add_argument("--motion-out", default=None, help="temporal: save the motion plane (.npy, float32 [H][W][2])")
+    ap.add_argument("--accumulated-film-out", default=None, help="temporal: save the accumulated XYZW film (.npy)")
     ap.add_argument("--rng-mode", choices=("reference", "pixel"), default="reference",
                     help="pixel: one RNG stream per pixel sample (the plain uniform frame only)")
     args = ap.parse_args(argv)
@@ -255,6 +277,29 @@ def main(argv=None) -> int:
             return 1
     elif args.shutter_samples is not None:
         ap.error("--shutter-samples needs --shutter-camera or --shutter")
+    if not args.temporal:
+        for flag, given in (("--temporal-history", args.temporal_history), ("--temporal-depth-tol", args.temporal_depth_tol),
+                            ("--temporal-sigma", args.temporal_sigma), ("--motion-out", args.motion_out),
+                            ("--accumulated-film-out", args.accumulated_film_out)):
+            if given is not None:
+                print(f"[vpt] FATAL: {flag} needs --temporal", file=sys.stderr)
+                return 1
+    else:  # (checked before anything touches a device)
+        for why, on in (("it accumulates the frames of a sequence: it needs --frames or --camera-path",
+                         args.frames is None and args.camera_path is None),
+                        ("not with a shutter (--shutter / --shutter-camera): the depth pass refuses one", want_shutter),
+                        ("not with --volume-sequence: the medium moves and has no motion vectors", args.volume_sequence),
+                        ("not with --light-groups / --relight: the group planes have no history",
+                         want_groups or args.relight_from),
+                        ("not with --rng-mode pixel: that mode keeps no moment plane", args.rng_mode == "pixel")):
+            if on:
+                print(f"[vpt] FATAL: --temporal: {why} (README, Temporal accumulation)", file=sys.stderr)
+                return 1
+        for flag, v in (("--temporal-history", args.temporal_history), ("--temporal-depth-tol", args.temporal_depth_tol),
+                        ("--temporal-sigma", args.temporal_sigma)):
+            if v is not None and not v > 0.0:  # (also a NaN)
+                print(f"[vpt] FATAL: {flag} wants a number > 0", file=sys.stderr)
+                return 1
     if args.rng_mode == "pixel" and (args.adaptive is not None or args.denoise or want_groups):
         print("[vpt] FATAL: --rng-mode pixel renders the plain uniform frame only (not with --adaptive, --denoise or "
               "--light-groups)", file=sys.stderr)
@@ -276,7 +321,8 @@ def main(argv=None) -> int:
     outputs = {"output_path": args.output_path, "--film-out": args.film_out, "--alpha-out": args.alpha_out,
                "--waves-out": args.waves_out, "--denoised-film-out": args.denoised_film_out,
                "--moments-out": args.moments_out, "--event-log": args.event_log, "--groups-out": args.groups_out,
-               "--depth-out": args.depth_out, "--depth-reach-out": args.depth_reach_out}
+               "--depth-out": args.depth_out, "--depth-reach-out": args.depth_reach_out,
+               "--motion-out": args.motion_out, "--accumulated-film-out": args.accumulated_film_out}
     if sequence:
         problem = _sequence_problem(args, outputs)
         if problem:
@@ -295,9 +341,14 @@ def main(argv=None) -> int:
         return 1
 
     from . import image, traces, volumes
-    from .render import Integrator, TileProvider, matte_guides, render_adaptive, render_sequence, render_uniform, run
+    from .render import (Integrator, TemporalState, TileProvider, matte_guides, render_adaptive, render_sequence,
+                         render_uniform, run)
     from .scenes import (SynthGrid, camera_of, lerp_camera, orbit, read_camera, read_camera_path, read_configuration,
                          shutter_cameras, with_camera)
+
+    # --temporal reprojects through the default --depth-out planes, so that one call serves both when the user keeps them
+    temporal_levels = _parse_depth_opacity(_DEPTH_OPACITY) if args.temporal else None
+    temporal_state = []  # (the sequence's TemporalState, once its Integrator exists)
 
     def render_frame(it, tag="", paths=None):
         """One frame's device work, as the single-frame program does it -> what write_frame saves (host arrays).
@@ -315,7 +366,8 @@ def main(argv=None) -> int:
         if args.adaptive is not None:
             film, waves, err, info, *plane = render_adaptive(it, args.adaptive, min_waves=min(args.min_spp, cfg.num_waves),
                                                              step_waves=args.spp_step, max_waves=cfg.num_waves,
-                                                             fused=args.adaptive_fused, return_moments=args.denoise,
+                                                             fused=args.adaptive_fused,
+                                                             return_moments=args.denoise or args.temporal,
                                                              groups=want_groups)
             if want_groups:
                 res["groups"] = plane.pop()
@@ -336,7 +388,7 @@ def main(argv=None) -> int:
             ms = (time.perf_counter() - t0) * 1e3
             print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp, pixel RNG mode)",
                   file=sys.stderr)
-        elif args.denoise:  # the ordered frame with its moment plane (the feed keeps none)
+        elif args.denoise or args.temporal:  # the ordered frame with its moment plane (the feed keeps none)
             film, m2 = (t.cpu().numpy() for t in render_uniform(it))
             ms = (time.perf_counter() - t0) * 1e3
             print(f"[vpt] {tag}Rendering complete in {ms:.0f} ms ({cfg.width}x{cfg.height}, {cfg.num_waves} spp)",
@@ -379,6 +431,22 @@ def main(argv=None) -> int:
         if args.depth_out:
             res["depth"], res["reach"] = it.render_depth(depth_opacity, sub=args.depth_sub or 1, reach=True)
             emit("depth")
+        if args.temporal:
+            import numpy as np
+
+            shared = (args.depth_out and (args.depth_sub or 1) == 1 and depth_opacity.tobytes() == temporal_levels.tobytes())
+            tdepth = res["depth"] if shared else it.render_depth(temporal_levels, sub=1)
+            t1 = time.perf_counter()
+            acc = temporal_state[0].accumulate(it, film, m2, depth=tdepth, motion=bool(args.motion_out), hist_n=True)
+            res["acc_film"], res["acc_m2"] = acc[0], acc[1]
+            if args.motion_out:
+                res["motion"] = acc[2]
+            ms = (time.perf_counter() - t1) * 1e3
+            n_cur, n_hist = float(np.nansum(film[..., 3])), float(acc[-1].sum())
+            print(f"[vpt] {tag}Accumulated in {ms:.1f} ms: history adds {n_hist / max(n_cur, 1.0):.2f} x the frame's own "
+                  f"samples", file=sys.stderr)
+            emit("acc")
+            film, m2 = res["acc_film"], res["acc_m2"]  # (what --denoise filters and the PNG shows)
         if args.denoise:
             if args.denoise_no_guides:
                 guides = []
@@ -395,7 +463,7 @@ def main(argv=None) -> int:
         emit("png")
         return res
 
-    PIECES = ("waves", "events", "film", "groups", "alpha", "depth", "m2", "denoised", "png")
+    PIECES = ("waves", "events", "film", "groups", "alpha", "depth", "acc", "m2", "denoised", "png")
 
     def write_piece(piece, res, paths):
         """One of a frame's files, from what render_frame has produced (host work only)."""
@@ -418,12 +486,17 @@ def main(argv=None) -> int:
             np.save(paths["--depth-out"], res["depth"])
             if paths["--depth-reach-out"]:
                 np.save(paths["--depth-reach-out"], res["reach"])
+        elif piece == "acc" and "acc_film" in res:
+            if paths["--accumulated-film-out"]:
+                np.save(paths["--accumulated-film-out"], res["acc_film"])
+            if paths["--motion-out"]:
+                np.save(paths["--motion-out"], res["motion"])
         elif piece == "m2" and args.denoise and paths["--moments-out"]:
             np.save(paths["--moments-out"], res["m2"])
         elif piece == "denoised" and args.denoise and paths["--denoised-film-out"]:
             np.save(paths["--denoised-film-out"], res["denoised"])
         elif piece == "png":
-            film = res["denoised"] if args.denoise else res.get("relit", res["film"])
+            film = res["denoised"] if args.denoise else res.get("relit", res.get("acc_film", res["film"]))
             if args.alpha or args.alpha_foreground:
                 alpha = res["alpha"]
                 rgb = image.film_to_image(image.foreground_film(film, alpha, res["cfg"]) if args.alpha_foreground else film)
@@ -486,6 +559,9 @@ def main(argv=None) -> int:
         else:
             cfgs = [None] * args.frames  # (the volume alone changes)
         nframes = len(cfgs)
+        if args.temporal:  # independent noise per frame: with one seed every frame reuses the same job streams
+            for k, c in enumerate(cfgs):
+                c.seed = (int(cfg.seed) + k) & 0xFFFFFFFF
         shutters = None
         if args.shutter is not None:  # frame k: from its own camera by the fraction F towards frame k + 1's
             opens = [camera_of(c) for c in cfgs]
@@ -494,6 +570,10 @@ def main(argv=None) -> int:
         it = Integrator(cfgs[0] if cfgs[0] is not None else cfg, dens, temp, device=args.device)
         if args.rng_mode == "pixel":
             it.set_rng_mode(1)
+        if args.temporal:
+            temporal_state.append(TemporalState(it, levels=int(temporal_levels.size), max_history=args.temporal_history,
+                                                depth_tol=0.1 if args.temporal_depth_tol is None else args.temporal_depth_tol,
+                                                sigma_r=4.0 if args.temporal_sigma is None else args.temporal_sigma))
         t_seq = time.perf_counter()
 
         def frames():

@@ -132,6 +132,19 @@ class DenoiseParams(C.Structure):
 
 assert C.sizeof(DenoiseParams) == 32
 
+
+class TemporalParams(C.Structure):
+    """vpt_temporal_params (vpt_gpu_temporal)."""
+    _fields_ = [("n_levels", C.c_uint32), ("max_history", C.c_float), ("depth_tol", C.c_float), ("sigma_r", C.c_float),
+                ("rel_floor", C.c_float)]
+
+    @classmethod
+    def make(cls, n_levels=2, max_history=64.0, depth_tol=0.1, sigma_r=4.0, rel_floor=1e-3):
+        return cls(int(n_levels), float(max_history), float(depth_tol), float(sigma_r), float(rel_floor))
+
+
+assert C.sizeof(TemporalParams) == 20
+
 # vpt_event (include/vpt_gpu.h): one Logger line (src/worker.cpp:16-48)
 EVENT_DTYPE = np.dtype([("jid", "<u8"), ("pixel", "<u4"), ("seq", "<u4"), ("type", "<u4"), ("v", "<f4", (7,))])
 assert EVENT_DTYPE.itemsize == 48
@@ -312,6 +325,9 @@ def lib() -> C.CDLL:
         L.vpt_gpu_render_depth.argtypes = [vp, C.c_uint32, C.c_uint32, fp, vp, vp, vp]
     if hasattr(L, "vpt_gpu_denoise"):  # (older builds in A/B runs lack the denoiser)
         L.vpt_gpu_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, C.POINTER(vp), vp, vp, vp]
+    if hasattr(L, "vpt_gpu_temporal"):  # (older builds in A/B runs lack the temporal pass)
+        L.vpt_gpu_temporal.argtypes = [vp, C.POINTER(TemporalParams), vp, vp, vp, C.POINTER(ShutterCamera), vp, vp, vp,
+                                       vp, vp, vp, vp, vp]
     L.vpt_gpu_sync.argtypes = [vp]
     L.vpt_gpu_film_clear.argtypes = [vp]
     L.vpt_gpu_film_device_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]

@@ -34,6 +34,7 @@
 #include "vpt_ctx.h"
 #include "vpt_kernels.h"
 #include "vpt_denoise.h"
+#include "vpt_temporal.h"
 
 namespace vpt {
 
@@ -1395,6 +1396,81 @@ int vpt_gpu_denoise(vpt_gpu_ctx* ctx, const vpt_denoise_params* p, const float* 
   if ((rc = release_slot(ctx, s, slot))) return rc;
   if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_denoise: ") + hipGetErrorString(e));
   if (er != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_denoise: ") + hipGetErrorString(er));
+  return VPT_OK;
+}
+
+int vpt_gpu_temporal(vpt_gpu_ctx* ctx, const vpt_temporal_params* p, const float* film_device, const float* m2_device,
+                     const float* depth_device, const vpt_shutter_camera* prev_cam, const float* hist_film_device,
+                     const float* hist_m2_device, const float* hist_depth_device, float* out_film_device,
+                     float* out_m2_device, float* motion_out_device, float* hist_n_out_device, void* hip_stream) {
+  // (the arguments are checked before the context, so that every refusal is testable without a device)
+  if (!p) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: null params");
+  if (!film_device || !m2_device || !depth_device)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: null film, moment plane or depth planes");
+  if (!out_film_device || !out_m2_device)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: null output film or output plane");
+  if (!prev_cam) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: null previous camera");
+  const int n_hist = (hist_film_device != nullptr) + (hist_m2_device != nullptr) + (hist_depth_device != nullptr);
+  if (n_hist != 0 && n_hist != 3)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: a history is a film, a plane and depth planes, or all three NULL");
+  if (p->n_levels < 1 || p->n_levels > vpt::kTemporalMaxLevels)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: n_levels must be 1..4");
+  if (!(p->max_history > 0.0f) || !(p->depth_tol > 0.0f) || !(p->sigma_r > 0.0f) || !(p->rel_floor > 0.0f))
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: max_history, depth_tol, sigma_r and rel_floor must be > 0");
+  // (float4 loads and stores on the films; the planes are read and written as floats)
+  if (((uintptr_t)film_device | (uintptr_t)hist_film_device | (uintptr_t)out_film_device) % 16 != 0 ||
+      ((uintptr_t)m2_device | (uintptr_t)depth_device | (uintptr_t)hist_m2_device | (uintptr_t)hist_depth_device |
+       (uintptr_t)out_m2_device | (uintptr_t)motion_out_device | (uintptr_t)hist_n_out_device) % 4 != 0)
+    return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: the films must be 16-byte aligned, the planes 4-byte aligned");
+  if (const char* why = vpt::camera_invalid(prev_cam->position, prev_cam->look, prev_cam->up, prev_cam->vfov_deg))
+    return vpt::set_error(VPT_E_INVALID, std::string("vpt_gpu_temporal: previous camera: ") + why);
+  if (!ctx) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: null context");
+  const size_t N = (size_t)ctx->scene.W * (size_t)ctx->scene.H, pb = N * sizeof(float);
+  {
+    const struct { const void* ptr; size_t bytes; } in[6] = {{film_device, 4 * pb}, {m2_device, pb},
+        {depth_device, p->n_levels * pb}, {hist_film_device, 4 * pb}, {hist_m2_device, pb},
+        {hist_depth_device, p->n_levels * pb}},
+        out[4] = {{out_film_device, 4 * pb}, {out_m2_device, pb}, {motion_out_device, 2 * pb}, {hist_n_out_device, pb}};
+    bool alias = false;
+    for (int o = 0; o < 4; ++o) {
+      for (int i = 0; i < 6; ++i) alias = alias || ranges_overlap(out[o].ptr, out[o].bytes, in[i].ptr, in[i].bytes);
+      for (int o2 = o + 1; o2 < 4; ++o2) alias = alias || ranges_overlap(out[o].ptr, out[o].bytes, out[o2].ptr, out[o2].bytes);
+    }
+    if (alias) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: an output overlaps an input or another output");
+  }
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  vpt::TemporalArgs A{};
+  A.W = ctx->scene.W;
+  A.H = ctx->scene.H;
+  A.n_levels = p->n_levels;
+  A.has_history = n_hist == 3;
+  A.max_history = p->max_history;
+  A.depth_tol = p->depth_tol;
+  A.sigma_r = p->sigma_r;
+  A.rel_floor = p->rel_floor;
+  // The current camera is the scene's, in a shutter entry's layout; the previous one by the shutter's own derivation.
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) A.cur[4 * i + j] = ctx->scene.cam_L[3 * i + j];
+    A.cur[4 * i + 3] = ctx->scene.cam_t[i];
+    A.cur[12 + i] = ctx->scene.cam_pos[i];
+  }
+  float prev[16];
+  vpt::shutter_entry(*prev_cam, A.W, A.H, prev);
+  vpt::temporal_prev_constants(prev, A);
+  const dim3 block(vpt::kTemporalBlockX, vpt::kTemporalBlockY);
+  const dim3 grid((unsigned)(((uint64_t)A.W + vpt::kTemporalBlockX - 1) / vpt::kTemporalBlockX),
+                  (unsigned)(((uint64_t)A.H + vpt::kTemporalBlockY - 1) / vpt::kTemporalBlockY));
+  if (grid.y > 65535u) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_temporal: more than 262140 rows");
+  hipStream_t s = (hipStream_t)hip_stream;
+  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the pass as for any launch)
+  if ((rc = take_slot(ctx, s, slot))) return rc;
+  hipLaunchKernelGGL(vpt::vpt_temporal_kernel, grid, block, 0, s, A, reinterpret_cast<const float4*>(film_device), m2_device,
+                     depth_device, reinterpret_cast<const float4*>(hist_film_device), hist_m2_device, hist_depth_device,
+                     reinterpret_cast<float4*>(out_film_device), out_m2_device, motion_out_device, hist_n_out_device);
+  const hipError_t e = hipGetLastError();
+  if ((rc = release_slot(ctx, s, slot))) return rc;
+  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_temporal: ") + hipGetErrorString(e));
   return VPT_OK;
 }
 

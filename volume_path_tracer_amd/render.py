@@ -431,6 +431,63 @@ class Integrator:
             return (out.cpu().numpy(), var.cpu().numpy()) if variance else out.cpu().numpy()
         return (out, var) if variance else out
 
+    def temporal(self, film, m2, depth, prev_camera, history=None, max_history=None, depth_tol: float = 0.1,
+                 sigma_r: float = 4.0, rel_floor: float = 1e-3, motion: bool = False, hist_n: bool = False, stream=None,
+                 out=None):
+        """`film` ([H][W][4]) and its moment plane `m2` ([H][W]) with the previous frame's accumulated film added
+        (vpt_gpu_temporal): `history` = (film, m2, depth) of the previous frame is reprojected through this frame's
+        depth planes `depth` ([K][H][W], what render_depth returns; sub=1) from the Integrator's current camera into
+        `prev_camera`, the camera the history was rendered with (a dict of set_camera's keywords; an absent key keeps
+        the scene's value).  history=None: the film and plane pass through.  max_history caps the history's sample
+        count per pixel (None: 4 * cfg.num_waves); depth_tol is the relative depth tolerance of a history tap; sigma_r
+        and rel_floor scale the rejection on Y.  -> (film, m2), an ordinary film and plane (the next frame's history,
+        with `depth` and the current camera); motion=True / hist_n=True append the motion plane ([H][W][2], pixels the
+        point moved from this frame's raster to the previous one's; NaN where it has no projection) and the history
+        count added per pixel ([H][W]).  Takes device tensors or numpy arrays and returns the same kind (what `film`
+        is); the inputs are not changed.  With tensors the call is asynchronous on `stream` (default: the current
+        one).  out: (film, m2) device tensors to write instead of new ones (render.TemporalState's buffers)."""
+        from .scenes import shutter_entries
+
+        torch = self.torch
+        as_numpy = not torch.is_tensor(film)
+        H, W = self.cfg.height, self.cfg.width
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        cam = shutter_entries(self.cfg, [dict(prev_camera)])
+
+        def dev(a, shape):
+            t = a if torch.is_tensor(a) else torch.from_numpy(np.array(a, dtype=np.float32, order="C"))  # (a copy)
+            t = t.to(device=self.dev, dtype=torch.float32).contiguous()
+            if shape[0] is None:
+                shape = (t.shape[0] if t.dim() == 3 else -1,) + shape[1:]
+            if tuple(t.shape) != shape:
+                raise ValueError(f"temporal: expected a plane of shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        with torch.cuda.stream(s):
+            f, m, d = dev(film, (H, W, 4)), dev(m2, (H, W)), dev(depth, (None, H, W))
+            K = int(d.shape[0])
+            if not 1 <= K <= 4:
+                raise ValueError("temporal: 1..4 depth planes")
+            hf = hm = hd = None
+            if history is not None:
+                hf, hm, hd = history
+                hf, hm, hd = dev(hf, (H, W, 4)), dev(hm, (H, W)), dev(hd, (K, H, W))
+            of, om = (torch.empty_like(f), torch.empty_like(m)) if out is None else out
+            mv = torch.empty((H, W, 2), dtype=torch.float32, device=self.dev) if motion else None
+            hn = torch.empty((H, W), dtype=torch.float32, device=self.dev) if hist_n else None
+        if max_history is None:
+            max_history = 4 * int(self.cfg.num_waves)
+        p = capi.TemporalParams.make(K, max_history, depth_tol, sigma_r, rel_floor)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        capi.check(capi.lib().vpt_gpu_temporal(self.h, C.byref(p), ptr(f), ptr(m), ptr(d), cam, ptr(hf), ptr(hm), ptr(hd),
+                                               ptr(of), ptr(om), ptr(mv), ptr(hn), C.c_void_p(int(s.cuda_stream))),
+                   "vpt_gpu_temporal")
+        res = (of, om) + ((mv,) if motion else ()) + ((hn,) if hist_n else ())
+        if as_numpy:
+            s.synchronize()
+            return tuple(t.cpu().numpy() for t in res)
+        return res
+
     def trace_jobs(self, jid_begin: int, jid_count: int, capacity: int = 1 << 20, film=None, stream=None):
         """Render jobs and return their Logger events (worker.cpp:16-48) as a numpy array of
         capi.EVENT_DTYPE sorted by (jid, seq).  Raises if more than `capacity` events occur."""
@@ -863,6 +920,52 @@ def render_sequence(it: Integrator, frames, render_frame, sink, depth: int = 2) 
         raise failed[0]
     return {"frames": n, "update_ms": update_ms, "render_ms": render_ms,
             "total_ms": (time.perf_counter() - t_begin) * 1e3}
+
+
+TEMPORAL_DEPTH_LEVELS = (1.0 / 255.0, 0.5)  # the depth planes a sequence reprojects through (render_depth, sub=1)
+
+
+class TemporalState:
+    """The history of a sequence's temporal accumulation (Integrator.temporal) across the frames of render_sequence:
+    two buffer sets (accumulated film, its moment plane, the depth planes) that swap roles every frame -- one is the
+    history the pass reads, the other receives its output -- and the camera the history was rendered with.
+    accumulate() runs one frame; reset() forgets the history (a cut: the next frame passes through)."""
+
+    def __init__(self, it: Integrator, levels: int = len(TEMPORAL_DEPTH_LEVELS), max_history=None, depth_tol: float = 0.1,
+                 sigma_r: float = 4.0, rel_floor: float = 1e-3):
+        torch = it.torch
+        H, W = it.cfg.height, it.cfg.width
+        self.params = dict(max_history=max_history, depth_tol=depth_tol, sigma_r=sigma_r, rel_floor=rel_floor)
+        self.sets = [{"film": torch.zeros((H, W, 4), dtype=torch.float32, device=it.dev),
+                      "m2": torch.zeros((H, W), dtype=torch.float32, device=it.dev),
+                      "depth": torch.zeros((int(levels), H, W), dtype=torch.float32, device=it.dev)} for _ in range(2)]
+        self.history = None  # index of the set that holds the history, None before the first frame
+        self.camera = None   # the camera that set was rendered with (scenes.camera_of)
+        self.frames = 0      # frames accumulated since the last reset
+
+    def reset(self) -> None:
+        self.history, self.camera, self.frames = None, None, 0
+
+    def accumulate(self, it: Integrator, film, m2, depth=None, motion: bool = False, hist_n: bool = False):
+        """One frame: `film` and `m2` (the frame as rendered) plus the history -> the accumulated (film, m2[, motion]
+        [, hist_n]): numpy arrays for numpy inputs, else device tensors -- the state's own buffers, which stay valid
+        until the frame after the next.  depth: this
+        frame's depth planes (numpy or tensor; None: render_depth(TEMPORAL_DEPTH_LEVELS, sub=1) here).  The output,
+        the depth planes and the Integrator's camera then become the history."""
+        from .scenes import camera_of
+
+        if depth is None:
+            depth = it.render_depth(TEMPORAL_DEPTH_LEVELS, sub=1)
+        out = self.sets[1 if self.history == 0 else 0]
+        hist = self.sets[self.history] if self.history is not None else None
+        out["depth"].copy_(it.torch.as_tensor(depth, dtype=it.torch.float32))
+        cam = camera_of(it.cfg)
+        res = it.temporal(film, m2, out["depth"], self.camera if hist is not None else cam,
+                          None if hist is None else (hist["film"], hist["m2"], hist["depth"]), motion=motion, hist_n=hist_n,
+                          out=(out["film"], out["m2"]), **self.params)
+        self.history, self.camera = (1 if self.history == 0 else 0), cam
+        self.frames += 1
+        return res
 
 
 def matte_guides(it: Integrator, sub: int = 1):
