@@ -1,6 +1,6 @@
 """ctypes binding of tests/native/denoise_host.cpp: the denoiser's per-pixel functions (csrc/vpt_denoise.h, the code
 the vpt_denoise kernels run per lane) over a frame on the CPU.  The library is compiled with hipcc, host only, like
-alpha_lib.py compiles alpha_host.cpp (tests/native/Makefile does not know it): on first use, or ahead of the tests by
+alpha_lib.py compiles matte_host.cpp (tests/native/Makefile does not know it): on first use, or ahead of the tests by
 __graft_entry__.build()."""
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 """tests/native/dense_pool_host.cpp as a program: the direct-addressed stencil pool's expansion and lookups on the
-CPU.  Compiled with hipcc, host only, like tests/alpha_lib.py compiles alpha_host.cpp (tests/native/Makefile does not
+CPU.  Compiled with hipcc, host only, like tests/alpha_lib.py compiles matte_host.cpp (tests/native/Makefile does not
 know it): on first use, or ahead of the tests by __graft_entry__.build()."""
 from __future__ import annotations
 

@@ -1,63 +1,15 @@
-"""ctypes binding of tests/native/depth_host.cpp: the depth pass's march (csrc/vpt_depth.h, the code vpt_depth_kernel
-runs per lane) on the CPU.  Compiled with hipcc, host only, as tests/alpha_lib.py compiles alpha_host.cpp
-(tests/native/Makefile does not know it): on first use, or ahead of the tests by __graft_entry__.build()."""
+"""ctypes binding of tests/native/matte_host.cpp, the depth pass's part: the march of csrc/vpt_depth.h (the code
+vpt_depth_kernel runs per lane) on the CPU.  One library with the coverage pass's part: tests/alpha_lib.py compiles and
+loads it."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
-from volume_path_tracer_amd.capi import Configuration, GridDesc
+from alpha_lib import CSRC, ROOT, _fp, build_lib, compile_host, lib  # noqa: F401  (this module's callers use them)
 
-ROOT = Path(__file__).resolve().parents[1]
-NATIVE = ROOT / "tests" / "native"
-CSRC = ROOT / "volume_path_tracer_amd" / "csrc"
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = [NATIVE / "depth_host.cpp", CSRC / "vpt_scene.cpp", CSRC / "vpt_grid_build.cpp", CSRC / "vpt_config.cpp"]
-# alpha_lib's float flags: no contraction, the device's semantics on the host
-FLAGS = ["-std=c++20", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "--cuda-host-only",
-         "-I" + str(ROOT / "include")]
-LIB = NATIVE / "build" / "libvpt_depth_host.so"
 BISECT_STEPS = 16  # kDepthBisectSteps (csrc/vpt_depth.h, stated in include/vpt_gpu.h)
-_L = None
-
-
-def compile_host(out: Path, extra=()) -> Path:
-    """hipcc, host only: the library (extra = ["-O2", "-shared"]) or the stand-alone program (-DDEPTH_HOST_MAIN)."""
-    out.parent.mkdir(parents=True, exist_ok=True)
-    r = subprocess.run([HIPCC, *FLAGS, *extra, "-o", str(out), *map(str, SOURCES)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return out
-
-
-def build_lib() -> Path:
-    deps = SOURCES + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "vpt_gpu.h"]
-    if not LIB.exists() or LIB.stat().st_mtime < max(p.stat().st_mtime for p in deps):
-        tmp = LIB.with_name(f"{LIB.name}.{os.getpid()}.tmp")
-        compile_host(tmp, ["-O2", "-shared"])
-        os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _L
-    if _L is None:
-        build_lib()
-        import torch  # noqa: F401  (hipcc links libamdhip64: torch's runtime first, see capi.lib())
-        L = C.CDLL(str(LIB))
-        cfgp, gp, fp, ip = C.POINTER(Configuration), C.POINTER(GridDesc), C.POINTER(C.c_float), C.POINTER(C.c_int32)
-        L.vptd_levels.argtypes = [C.c_uint32, fp, fp]
-        L.vptd_render.argtypes = [cfgp, gp, C.c_uint32, C.c_uint32, fp, fp, fp]
-        L.vptd_tau_upto.argtypes = [cfgp, gp, ip, ip, fp, C.c_uint64, fp]
-        _L = L
-    return _L
-
-
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 def levels(opacity):

@@ -1,6 +1,6 @@
 """ctypes binding of tests/native/eval_split_host.cpp: the device state machine on the CPU in two environments, the
 density evaluation whole or split (Env::kEvalSplit).  The library is compiled with hipcc, host only, like
-tests/alpha_lib.py compiles alpha_host.cpp (tests/native/Makefile does not know it): on first use, or ahead of the
+tests/alpha_lib.py compiles matte_host.cpp (tests/native/Makefile does not know it): on first use, or ahead of the
 tests by __graft_entry__.build()."""
 from __future__ import annotations
 

@@ -1,5 +1,5 @@
 """The coverage (alpha) pass, host side (no GPU): the march of csrc/vpt_alpha.h -- the code vpt_alpha_kernel runs per
-lane -- compiled for the CPU (tests/native/alpha_host.cpp, bound by tests/alpha_lib.py) against the float64 optical
+lane -- compiled for the CPU (tests/native/matte_host.cpp, bound by tests/alpha_lib.py) against the float64 optical
 depths of tests/analytic_anchor.py, against the integrator's own collision statistics, over the scene-parameter
 space; the RGBA PNG path and foreground_film of image.py; the ABI entry vpt_gpu_render_alpha."""
 import ctypes as C

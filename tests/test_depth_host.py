@@ -1,5 +1,5 @@
 """The depth pass, host side (no GPU): the march of csrc/vpt_depth.h -- the code vpt_depth_kernel runs per lane --
-compiled for the CPU (tests/native/depth_host.cpp, bound by tests/depth_lib.py) against the float64 inverse of the
+compiled for the CPU (tests/native/matte_host.cpp, bound by tests/depth_lib.py) against the float64 inverse of the
 analytic anchors' cumulative optical depth, against the matte's tau plane (bit-exact reach equivalence), against its own
 march cut at the depth, and against the first real collisions of the reference's paths; the command line's refusals;
 the ABI entry vpt_gpu_render_depth."""

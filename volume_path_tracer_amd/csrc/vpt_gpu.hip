@@ -1011,6 +1011,33 @@ void launch_denoise_atrous(bool last, dim3 grid, dim3 block, hipStream_t s, cons
     hipLaunchKernelGGL((vpt::vpt_denoise_atrous_kernel<G, false>), grid, block, 0, s, A, step, src, gd, dst, film, out_film,
                        var_out);
 }
+
+// The matte passes' launch (vpt_gpu_render_alpha, vpt_gpu_render_depth), after the entry `fn` has checked its own
+// arguments: the context's state, the tile ranks, a launch slot, and launch(blocks, stream) -- one wavefront per
+// (tile slot, chunk of 64 pixels).  `noun` is what a shutter would leave the scene camera's alone.
+template <class Launch>
+int matte_pass(vpt_gpu_ctx* ctx, const char* fn, const char* noun, void* hip_stream, Launch launch) {
+  int rc = ctx_device(ctx);
+  if (rc) return rc;
+  const auto refuse = [fn](int code, const std::string& what) { return vpt::set_error(code, std::string(fn) + ": " + what); };
+  if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
+    return refuse(VPT_E_STATE, "a feed of this context is open");
+  if (!ctx->shutter.empty())
+    return refuse(VPT_E_STATE, std::string("a shutter is attached and the ") + noun +
+                                   " would be the scene camera's alone: detach it (vpt_gpu_set_shutter NULL, 0)");
+  if (!ctx->volume_ok) return volume_gone();
+  if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
+  const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
+  if (blocks >= (1ULL << 31)) return refuse(VPT_E_INVALID, "2^31 or more pixel chunks");
+  hipStream_t s = (hipStream_t)hip_stream;
+  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the pass as for any launch)
+  if ((rc = take_slot(ctx, s, slot))) return rc;
+  launch(dim3((unsigned)blocks), s);
+  const hipError_t e = hipGetLastError();
+  if ((rc = release_slot(ctx, s, slot))) return rc;
+  if (e != hipSuccess) return refuse(VPT_E_HIP, hipGetErrorString(e));
+  return VPT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1245,26 +1272,10 @@ int vpt_gpu_render_alpha(vpt_gpu_ctx* ctx, uint32_t sub, float* alpha_device, fl
   if (!alpha_device) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: null alpha plane");
   if (sub < 1 || sub > vpt::kAlphaMaxSub)
     return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: sub-rays per axis must be 1..8");
-  int rc = ctx_device(ctx);
-  if (rc) return rc;
-  if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
-    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_alpha: a feed of this context is open");
-  if (!ctx->shutter.empty())
-    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_alpha: a shutter is attached and the matte would be the scene "
-                                       "camera's alone: detach it (vpt_gpu_set_shutter NULL, 0)");
-  if (!ctx->volume_ok) return volume_gone();
-  if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
-  const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
-  if (blocks >= (1ULL << 31)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_alpha: 2^31 or more pixel chunks");
-  hipStream_t s = (hipStream_t)hip_stream;
-  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the pass as for any launch)
-  if ((rc = take_slot(ctx, s, slot))) return rc;
-  hipLaunchKernelGGL(vpt::vpt_alpha_kernel, dim3((unsigned)blocks), dim3(64), 0, s, ctx->scene_dev,
-                     (const uint32_t*)ctx->order, sub, alpha_device, tau_device);
-  const hipError_t e = hipGetLastError();
-  if ((rc = release_slot(ctx, s, slot))) return rc;
-  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_render_alpha: ") + hipGetErrorString(e));
-  return VPT_OK;
+  return matte_pass(ctx, "vpt_gpu_render_alpha", "matte", hip_stream, [&](dim3 blocks, hipStream_t s) {
+    hipLaunchKernelGGL(vpt::vpt_alpha_kernel, blocks, dim3(64), 0, s, ctx->scene_dev, (const uint32_t*)ctx->order, sub,
+                       alpha_device, tau_device);
+  });
 }
 
 int vpt_gpu_render_depth(vpt_gpu_ctx* ctx, uint32_t sub, uint32_t n_levels, const float* opacity_host, float* depth_device,
@@ -1276,26 +1287,10 @@ int vpt_gpu_render_depth(vpt_gpu_ctx* ctx, uint32_t sub, uint32_t n_levels, cons
   vpt::DepthLevels levels;  // (tau_k = -log1p(-a_k), once, here)
   if (const char* why = vpt::depth_levels(n_levels, opacity_host, levels))
     return vpt::set_error(VPT_E_INVALID, std::string("vpt_gpu_render_depth: ") + why);
-  int rc = ctx_device(ctx);
-  if (rc) return rc;
-  if (ctx->open_feeds.load() > 0)  // (the launch would queue behind the feed's, which holds the device)
-    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_depth: a feed of this context is open");
-  if (!ctx->shutter.empty())
-    return vpt::set_error(VPT_E_STATE, "vpt_gpu_render_depth: a shutter is attached and the depth would be the scene "
-                                       "camera's alone: detach it (vpt_gpu_set_shutter NULL, 0)");
-  if (!ctx->volume_ok) return volume_gone();
-  if ((rc = ensure_order(ctx))) return rc;  // (the tile ranks: computed by the context's first call that needs them)
-  const uint64_t blocks = ctx->scene.T * (((uint64_t)ctx->scene.tile_area + 63u) / 64u);
-  if (blocks >= (1ULL << 31)) return vpt::set_error(VPT_E_INVALID, "vpt_gpu_render_depth: 2^31 or more pixel chunks");
-  hipStream_t s = (hipStream_t)hip_stream;
-  uint32_t slot = 0;  // (a ring slot, so that vpt_gpu_sync and scene updates wait for the pass as for any launch)
-  if ((rc = take_slot(ctx, s, slot))) return rc;
-  hipLaunchKernelGGL(vpt::vpt_depth_kernel, dim3((unsigned)blocks), dim3(64), 0, s, ctx->scene_dev,
-                     (const uint32_t*)ctx->order, sub, levels, depth_device, reach_device);
-  const hipError_t e = hipGetLastError();
-  if ((rc = release_slot(ctx, s, slot))) return rc;
-  if (e != hipSuccess) return vpt::set_error(VPT_E_HIP, std::string("vpt_gpu_render_depth: ") + hipGetErrorString(e));
-  return VPT_OK;
+  return matte_pass(ctx, "vpt_gpu_render_depth", "depth", hip_stream, [&](dim3 blocks, hipStream_t s) {
+    hipLaunchKernelGGL(vpt::vpt_depth_kernel, blocks, dim3(64), 0, s, ctx->scene_dev, (const uint32_t*)ctx->order, sub,
+                       levels, depth_device, reach_device);
+  });
 }
 
 int vpt_gpu_denoise(vpt_gpu_ctx* ctx, const vpt_denoise_params* p, const float* film_device, const float* m2_device,

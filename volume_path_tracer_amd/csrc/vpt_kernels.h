@@ -1353,25 +1353,34 @@ __global__ __launch_bounds__(256) void vpt_relight_kernel(const float4* g, Relig
   out[p] = o;
 }
 
-// The coverage pass (vpt_gpu_render_alpha): alpha = 1 - mean exp(-tau) over each pixel's sub-rays, tau by the
-// deterministic march of vpt_alpha.h.  A block is one wavefront that owns up to 64 pixels of one tile, indexed as
-// vpt_band_order_kernel indexes them -- block = (tile slot, chunk of 64 pixels), lane p = pixel p of the chunk -- so
-// a wavefront's 64 rays walk the same cells and read the same stencils.  Tile slot b renders tile rank[b], the
-// context's descending-cost order: the long rays start first and the short ones fill the tail.  Lanes beyond a
-// ragged tile's pixels, and in single-pixel mode every lane but that pixel's, end at once.  No LDS, no atomics,
-// nothing shared between blocks; every pixel of the frame is written exactly once.
-__global__ __launch_bounds__(64) void vpt_alpha_kernel(const DevScene* scene, const uint32_t* rank, uint32_t sub,
-                                                       float* alpha, float* tau) {
-  const DevScene& S = *scene;
+// The pixel of this lane in the matte passes' launch shape: a block is one wavefront that owns up to 64 pixels of one
+// tile, indexed as vpt_band_order_kernel indexes them -- block = (tile slot, chunk of 64 pixels), lane p = pixel p of
+// the chunk -- and tile slot b is tile rank[b].  False for a lane without a pixel: beyond a ragged tile's pixels, and
+// in single-pixel mode every lane but that pixel's.
+__device__ __forceinline__ bool matte_lane_pixel(const DevScene& S, const uint32_t* rank, int32_t& px, int32_t& py) {
   const uint32_t area = S.tile_area, chunks = (area + 63u) / 64u;
   const uint32_t tb = blockIdx.x / chunks, q = (blockIdx.x - tb * chunks) * 64u + threadIdx.x;
-  if ((uint64_t)tb >= S.T) return;
+  if ((uint64_t)tb >= S.T) return false;
   const uint32_t t = rank[tb];
   const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
   const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
-  if (q >= area || (int32_t)q >= rw * rh) return;
-  const int32_t yl = (int32_t)q / rw, px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
-  if (S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) return;
+  if (q >= area || (int32_t)q >= rw * rh) return false;
+  const int32_t yl = (int32_t)q / rw;
+  px = x0 + ((int32_t)q - yl * rw);
+  py = y0 + yl;
+  return !(S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y));
+}
+
+// The coverage pass (vpt_gpu_render_alpha): alpha = 1 - mean exp(-tau) over each pixel's sub-rays, tau by the
+// deterministic march of vpt_alpha.h.  A wavefront's 64 pixels are one tile's (matte_lane_pixel), so its 64 rays walk
+// the same cells and read the same stencils.  Tile slot b renders tile rank[b], the context's descending-cost order:
+// the long rays start first and the short ones fill the tail.  Lanes without a pixel end at once.  No LDS, no
+// atomics, nothing shared between blocks; every pixel of the frame is written exactly once.
+__global__ __launch_bounds__(64) void vpt_alpha_kernel(const DevScene* scene, const uint32_t* rank, uint32_t sub,
+                                                       float* alpha, float* tau) {
+  const DevScene& S = *scene;
+  int32_t px, py;
+  if (!matte_lane_pixel(S, rank, px, py)) return;
   float a, od;
   alpha_pixel(S, px, py, sub, a, od);
   const uint64_t p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
@@ -1380,23 +1389,15 @@ __global__ __launch_bounds__(64) void vpt_alpha_kernel(const DevScene* scene, co
 }
 
 // The depth pass (vpt_gpu_render_depth): per pixel and level the mean distance at which the optical depth of the
-// pixel's sub-rays first reaches the level, by the march of vpt_depth.h.  vpt_alpha_kernel's shape: a block is one
-// wavefront that owns up to 64 pixels of one tile, block = (tile slot, chunk of 64 pixels), lane p = pixel p of the
-// chunk, tile slot b renders tile rank[b].  The levels come by value (scalar loads, no per-lane table); a lane keeps
+// pixel's sub-rays first reaches the level, by the march of vpt_depth.h.  vpt_alpha_kernel's shape and pixels
+// (matte_lane_pixel).  The levels come by value (scalar loads, no per-lane table); a lane keeps
 // per level a sum and a count, and per ray the index of its next level.  A lane whose ray has stopped waits for its
 // wavefront's longest ray.  No LDS, no atomics, nothing shared between blocks; every pixel is written exactly once.
 __global__ __launch_bounds__(64) void vpt_depth_kernel(const DevScene* scene, const uint32_t* rank, uint32_t sub,
                                                        DepthLevels levels, float* depth, float* reach) {
   const DevScene& S = *scene;
-  const uint32_t area = S.tile_area, chunks = (area + 63u) / 64u;
-  const uint32_t tb = blockIdx.x / chunks, q = (blockIdx.x - tb * chunks) * 64u + threadIdx.x;
-  if ((uint64_t)tb >= S.T) return;
-  const uint32_t t = rank[tb];
-  const int32_t x0 = (int32_t)(t % (uint32_t)S.ntx) * S.tw, y0 = (int32_t)(t / (uint32_t)S.ntx) * S.th;
-  const int32_t rw = min(S.W - x0, S.tw), rh = min(S.H - y0, S.th);
-  if (q >= area || (int32_t)q >= rw * rh) return;
-  const int32_t yl = (int32_t)q / rw, px = x0 + ((int32_t)q - yl * rw), py = y0 + yl;
-  if (S.single_pixel_enabled && (px != S.sp_x || py != S.sp_y)) return;
+  int32_t px, py;
+  if (!matte_lane_pixel(S, rank, px, py)) return;
   float d[kDepthMaxLevels], r[kDepthMaxLevels];
   depth_pixel(S, px, py, sub, levels, d, r);
   const uint64_t plane = (uint64_t)S.H * (uint64_t)S.W, p = (uint64_t)py * (uint64_t)S.W + (uint64_t)px;
